@@ -14,10 +14,16 @@ counter-based RNG with seed 0x5EED0000 + tile_index, t_j = 0.05*j (BASELINE.md s
 (h0, omega) are resident in HBM before the timed region; outputs are the two finished RGBA32F maps
 in HBM (D2H read-back is not part of the metric).
 
-The K timed steps are K asynchronous ocean_compute_waves_async calls followed by one synchronise.
-With --depth 3 (default) consecutive frames rotate over three independent chains (own stream, own
-intermediates, own map set); every frame is still computed in full.  --depth 1 = strictly serial
-frames (also reported under extra).
+The K timed steps are K asynchronous ocean_compute_waves_async calls followed by one synchronise;
+ms_per_step is their time over K.  With --depth 3 (default) consecutive frames rotate over three
+independent chains (own stream, own intermediates, own map set); every frame is still computed in
+full.  --depth 1 = strictly serial frames (also reported under extra).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs
+DIR is given, and prints its line; `roofline`, `cpu_baseline`, `gather` and `timing` are null in it.
+Everything else described below -- the timing spread over --regions more regions, the per-kernel
+roofline passes, the gather, the secondary configurations, the CPU baseline and the sidecar -- is
+measured with --full only.
 
 roofline: per-launch durations are the kernels' own execution times (events attached to the dispatches with hipExtLaunchKernelGGL on the
 launch stream, serial frames in a context of their own so that every kernel has the GPU to itself; three such passes spread over the run --
@@ -26,8 +32,8 @@ bytes are what THIS pipeline has to move (73 B/texel: 23 / 28 / 22 per launch), 
 rocprofv3 duration of the same kernel (profiles/kernel_stats.json) beside them while the kernel sources hash to what those were measured with.
 
 Output: rank 0 prints ONE compact JSON line on stdout (the contract's keys + roofline / cpu_baseline / gather / timing objects, numbers and
-short labels only, < 8 KB: tests/test_bench_contract.py asserts it) and writes everything else it measured -- the secondary configurations,
-per-kernel tables, the CPU baseline's stage split, every explanatory note -- to bench_extra.json beside this script and to stderr.
+short labels only, < 8 KB: tests/test_bench_contract.py asserts it); with --full it writes everything else it measured -- the secondary
+configurations, per-kernel tables, the CPU baseline's stage split, every explanatory note -- to bench_extra.json beside this script and to stderr.
 
 Multi-GPU: tiles are independent, so every rank synthesises its own tile(s) with no data-path
 collective ("weak" scaling, value = frames of all ranks per second).  The north-star's single RCCL
@@ -79,15 +85,21 @@ def parse(argv=None):
     # warm-up frames measure 60 us/frame, every later batch of 200 measures 53-54 -- and 3000 frames are 0.2 s
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=1000)
-    ap.add_argument("--regions", type=int, default=9, help="timed regions of --steps frames each (>= 7): ms_per_step is their median, p10 / p90 beside it")
+    ap.add_argument("--regions", type=int, default=9, help="with --full: timed regions of --steps frames each (>= 7) behind the headline one; "
+                                                              "their median, p10 / p90 are the line's `timing`")
     ap.add_argument("--prewarm", type=int, default=2000, help="untimed frames before the W warm-up steps (brings the device to its steady state even when W is small: 0.1 s)")
     ap.add_argument("--size", type=int, default=2048, help="tile size N (default: the roofline config, 2048)")
     ap.add_argument("--tiles", type=int, default=1, help="independent tiles per rank per step")
     ap.add_argument("--depth", type=int, default=3, help="frame pipeline depth of the asynchronous API (1 = strictly serial frames)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline too: the timing spread over --regions, the "
+                                                        "per-kernel roofline passes, the RCCL gather, the secondary configurations, the CPU "
+                                                        "baseline, and the sidecar " + SIDECAR)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's "
+                                                                         "tiles) as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="budget for EACH of the two CPU baseline samples")
-    ap.add_argument("--no-gather", action="store_true", help="skip the RCCL gather measurement")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary 512^2 / batched measurements")
+    ap.add_argument("--no-gather", action="store_true", help="with --full: skip the RCCL gather measurement")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary 512^2 / batched measurements")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)   # internal: the CPU baseline leg as its own process
     ap.add_argument("--check-file", default=None, help=argparse.SUPPRESS)                  # internal: GPU frames the child checks against the float64 oracle
     return ap.parse_args(argv)
@@ -635,7 +647,7 @@ def build_line(args, world, n, tiles, frames_per_s, ms_per_step, roofline, gathe
                    "parallelism": f"tiles sharded 1 process per GPU x{world}, no data-path collective"},
         "gtexels_per_s": n * n * frames_per_s * 1e-9,
         "prewarm_frames": args.prewarm,
-        "timing": {"statistic": "median of regions", "regions": t.get("regions"), "ms_per_step_median": t.get("ms_per_step_median"),
+        "timing": {"statistic": "spread over regions", "regions": t.get("regions"), "ms_per_step_median": t.get("ms_per_step_median"),
                    "ms_per_step_mean": t.get("ms_per_step_mean"), "ms_per_step_p10": t.get("ms_per_step_p10"),
                    "ms_per_step_p90": t.get("ms_per_step_p90")} if t else None,
         "roofline": compact_roofline(roofline),
@@ -644,7 +656,7 @@ def build_line(args, world, n, tiles, frames_per_s, ms_per_step, roofline, gathe
         "gather": compact_gather(gather_obj),
         "kernel_source_sha16": kernel_source_sha16(),
         "build_id": build_id,
-        "sidecar": SIDECAR,
+        "sidecar": SIDECAR if args.full else None,
     }
     return _compact(line)
 
@@ -763,6 +775,30 @@ def gather_report(n, tiles, world, rccl_ranks, rccl_rank, compute_s, serial_s, o
             "root_copy_matches_local_maps": ok}
 
 
+DUMP_TEXELS_MAX = 1 << 20      # per map: two maps of 16 MiB + the sample's indices (8 MiB) stay well inside 64 MB
+
+
+def dump_outputs(b, out_dir):
+    """--dump-outputs: what the last timed step hands a caller of this path, as float32 .npy files in out_dir -- `displacement` and `normal`
+    (the RGBA32F maps of every tile, [tiles, N, N, 4]) and `heights` ([tiles, 3]: amplitude, min, max).  Maps of more than DUMP_TEXELS_MAX
+    texels are reduced to a fixed sample: DUMP_TEXELS_MAX texels drawn without replacement by a generator seeded with SEED, ascending
+    ([texels, 4]; their flat indices into [tiles, N, N] in `sample_index`, float64), the same texels in every run with the same arguments."""
+    import numpy as np
+    d, q = b.read_maps()                                       # (both read-outs wait for the frame enqueued last)
+    out = {"heights": np.array([b.heights(i) for i in range(b.tiles)], dtype=np.float32)}
+    texels = d.shape[0] * d.shape[1] * d.shape[2]
+    if texels <= DUMP_TEXELS_MAX:
+        out["displacement"], out["normal"] = d, q
+    else:
+        idx = np.sort(np.random.default_rng(SEED).choice(texels, DUMP_TEXELS_MAX, replace=False))
+        out["displacement"], out["normal"] = d.reshape(-1, 4)[idx], q.reshape(-1, 4)[idx]
+        out["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -853,19 +889,19 @@ def main():
         placed = bs.placement_report()
         bs.close()
         serial_passes.append((ms_i / nk * 1e3, kern_i, when, kern_cold, placed))
-    for j in range(min(args.prewarm, 200)):            # (the first frames of the process: module load, first touch)
-        b.compute_waves_async(DT * j)
-    sync()
-    serial_pass("before the timed regions")
+    if args.full:
+        for j in range(min(args.prewarm, 200)):        # (the first frames of the process: module load, first touch)
+            b.compute_waves_async(DT * j)
+        sync()
+        serial_pass("before the timed regions")
     for j in range(args.prewarm):                      # device pre-warm (clocks, caches, first touch of every chain's buffers)
         b.compute_waves_async(DT * j)
     sync()
     for j in range(args.warmup):
         b.compute_waves_async(DT * j)
-    # K timed regions of exactly --steps steps each, every one bracketed by barrier + synchronise on both sides and reduced to the MAX
-    # over ranks; ms_per_step / value come from the MEDIAN region, the spread (p10, p90, min, max) is reported beside it.
-    region_s = []
-    for r in range(args.regions):
+
+    def timed_region(r):
+        """Region r: exactly --steps steps, bracketed by barrier + synchronise on both sides; its time is the MAX over ranks."""
         sync(); barrier(); sync()
         t0 = time.perf_counter()
         for j in range(args.steps):
@@ -873,21 +909,67 @@ def main():
         sync()
         t1 = time.perf_counter()         # this rank's K steps are done; the closing barrier + synchronise follow, and the region's time is
         barrier(); sync()                # the MAX over ranks of (t1 - t0): all ranks left the opening barrier together, so that is the time
-        region_s.append(wdist.max_over_ranks(t1 - t0, device=red_dev))     # until the slowest one finished -- without the barrier's own latency
-    import numpy as _np
-    reg = _np.sort(_np.asarray(region_s, dtype=_np.float64))
-    elapsed = float(_np.median(reg))
+        return wdist.max_over_ranks(t1 - t0, device=red_dev)      # until the slowest one finished -- without the barrier's own latency
+
+    emitted = [False]
+
+    def emit(line_obj, sidecar_obj=None):
+        """rank 0: the sidecar (file beside this script + stderr), then the ONE JSON line through the saved stdout descriptor; at most once"""
+        if rank != 0 or emitted[0]:
+            return
+        emitted[0] = True
+        import ctypes
+        data = encode_line(line_obj)
+        if sidecar_obj is not None:
+            text = json.dumps(sidecar_obj, indent=1, default=str)
+            try:
+                with open(os.path.join(ROOT, SIDECAR), "w") as f:
+                    f.write(text + "\n")
+            except OSError as exc:                    # a read-only checkout: stderr still carries it
+                print(f"bench.py: could not write {SIDECAR}: {exc}", file=sys.stderr)
+            print("bench.py sidecar (" + SIDECAR + "):\n" + text, file=sys.stderr)
+        sys.stdout.flush(); sys.stderr.flush()
+        ctypes.CDLL(None).fflush(None)            # C stdio buffers (the RCCL banner) leave through the redirected descriptor
+        os.write(json_fd, data)
+
+    def teardown():
+        if world > 1:
+            import threading
+            # the line is out: a stuck teardown must not hold the launcher -- but it is a failure, and reported as one
+            t = threading.Timer(300.0, lambda: os._exit(4))     # (rank 0 arrives after its CPU baseline leg: up to ~2 minutes)
+            t.daemon = True
+            t.start()
+            dist.barrier()
+            dist.destroy_process_group()
+            t.cancel()
+
+    # the headline: ONE region of exactly --steps steps
+    elapsed = timed_region(0)
     ms_per_step = elapsed / args.steps * 1e3
     frames_per_s = world * tiles * args.steps / elapsed
-    timing_stats = {"regions": args.regions, "steps_per_region": args.steps, "statistic": "median over the regions",
-                    "ms_per_step_median": ms_per_step,
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(b, args.dump_outputs)
+        print(f"bench.py: wrote {', '.join(k + '.npy' for k in dumped)} to {args.dump_outputs}", file=sys.stderr)
+    if not args.full:
+        b.close()
+        emit(build_line(args, world, n, tiles, frames_per_s, ms_per_step, None, None, None, None, None, build_id))
+        teardown()
+        return
+    # --full: K more regions of --steps steps each, back to back, for the spread (p10, p90, min, max) beside the headline (SURVEY.md 8d)
+    region_s = [timed_region(r) for r in range(1, args.regions + 1)]
+    import numpy as _np
+    reg = _np.sort(_np.asarray(region_s, dtype=_np.float64))
+    timing_stats = {"regions": args.regions, "steps_per_region": args.steps,
+                    "statistic": "spread over the regions behind the headline one (ms_per_step = the headline region)",
+                    "ms_per_step_headline": ms_per_step,
+                    "ms_per_step_median": float(_np.median(reg)) / args.steps * 1e3,
                     "ms_per_step_mean": float(reg.mean()) / args.steps * 1e3,
                     "ms_per_step_p10": float(_np.percentile(reg, 10)) / args.steps * 1e3,
                     "ms_per_step_p90": float(_np.percentile(reg, 90)) / args.steps * 1e3,
                     "ms_per_step_min": float(reg[0]) / args.steps * 1e3, "ms_per_step_max": float(reg[-1]) / args.steps * 1e3,
                     "ms_per_step_of_each_region_in_order": [x / args.steps * 1e3 for x in region_s],
                     "what": "each region = exactly `steps` asynchronous frames between barrier + ocean_synchronize + torch.cuda.synchronize "
-                            "on both sides, max over ranks; regions run back to back after the warm-up"}
+                            "on both sides, max over ranks; the headline region and then `regions` more run back to back after the warm-up"}
 
     # ---- per-kernel durations (kernel execution time from events attached to the dispatches), measured with
     # serial frames -- a per-launch duration only characterises a kernel that has the GPU to itself; the
@@ -938,26 +1020,6 @@ def main():
 
     # ---- the exchange step: RCCL gather of the packed maps, outside the timed region
     gather = None
-    emitted = [False]
-
-    def emit(line_obj, sidecar_obj=None):
-        """rank 0: the sidecar (file beside this script + stderr), then the ONE JSON line through the saved stdout descriptor; at most once"""
-        if rank != 0 or emitted[0]:
-            return
-        emitted[0] = True
-        import ctypes
-        data = encode_line(line_obj)
-        if sidecar_obj is not None:
-            text = json.dumps(sidecar_obj, indent=1, default=str)
-            try:
-                with open(os.path.join(ROOT, SIDECAR), "w") as f:
-                    f.write(text + "\n")
-            except OSError as exc:                    # a read-only checkout: stderr still carries it
-                print(f"bench.py: could not write {SIDECAR}: {exc}", file=sys.stderr)
-            print("bench.py sidecar (" + SIDECAR + "):\n" + text, file=sys.stderr)
-        sys.stdout.flush(); sys.stderr.flush()
-        ctypes.CDLL(None).fflush(None)            # C stdio buffers (the RCCL banner) leave through the redirected descriptor
-        os.write(json_fd, data)
 
     def headline(gather_obj, extra_obj, cpu, cpu_strong):
         line = build_line(args, world, n, tiles, frames_per_s, ms_per_step, roofline, gather_obj, cpu, cpu_strong, timing_stats, build_id)
@@ -1045,15 +1107,7 @@ def main():
         out = headline(gather, extra, cpu, cpu_strong)
     emit(*out)
     failed = isinstance(gather, dict) and "error" in gather
-    if world > 1:
-        import threading
-        # the line is out: a stuck teardown must not hold the launcher -- but it is a failure, and reported as one
-        t = threading.Timer(300.0, lambda: os._exit(4))     # (rank 0 arrives after its CPU baseline leg: up to ~2 minutes)
-        t.daemon = True
-        t.start()
-        dist.barrier()
-        dist.destroy_process_group()
-        t.cancel()
+    teardown()
     if failed:
         sys.exit(3)
 

@@ -183,7 +183,7 @@ def test_product_path_never_imports_oracle():
     subprocess.run([sys.executable, "-c", code], check=True, cwd=ROOT)
 
 
-REFERENCE_METHODS = [  # /root/reference/src/scene/WSTessendorf.h:58-122
+REFERENCE_METHODS = [  # the reference's src/scene/WSTessendorf.h:58-122
     "Prepare", "ComputeWaves", "GetTileSize", "GetTileLength", "GetWindDir", "GetWindSpeed", "GetAnimationPeriod",
     "GetPhillipsConst", "GetDamping", "GetDisplacementLambda", "GetMinHeight", "GetMaxHeight",
     "GetDisplacementCount", "GetDisplacements", "GetNormalCount", "GetNormals", "SetTileSize", "SetTileLength",
@@ -191,32 +191,27 @@ REFERENCE_METHODS = [  # /root/reference/src/scene/WSTessendorf.h:58-122
 ]
 
 
+def reference_header():
+    """What tests/golden/reference_header.json recorded from the reference's WSTessendorf.h: the public methods and the default
+    constants' initialisers (the reference tree itself is not part of this repository)."""
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "reference_header.json")))
+
+
 def test_reference_method_list_is_the_reference_headers():
-    """Where the reference tree is present (the build container; never the GPU box) the list above is checked against the
-    public section of its header: every public method of WSTessendorf, none missing, none invented."""
-    hdr_path = "/root/reference/src/scene/WSTessendorf.h"
-    if not os.path.exists(hdr_path):
-        pytest.skip("reference tree not present")
-    text = open(hdr_path).read()
-    public = text[text.index("public:"):text.index("private:")]
-    public = re.sub(r"/\*.*?\*/", "", public, flags=re.S)
-    public = re.sub(r"//[^\n]*", "", public)
-    names = set(re.findall(r"\b((?:Get|Set)[A-Za-z]+|Prepare|ComputeWaves)\s*\(", public))
+    """The list above against the public section of the reference's header: every public method of WSTessendorf, none missing,
+    none invented."""
+    names = set(reference_header()["public_methods"])
     assert names == set(REFERENCE_METHODS), (sorted(names - set(REFERENCE_METHODS)), sorted(set(REFERENCE_METHODS) - names))
 
 
 def test_default_parameters_are_the_reference_headers(abi):
-    """ocean_default_params against the s_kDefault* constants and the m_Lambda initialiser parsed from the reference header
-    (build container only)."""
-    hdr_path = "/root/reference/src/scene/WSTessendorf.h"
-    if not os.path.exists(hdr_path):
-        pytest.skip("reference tree not present")
-    text = open(hdr_path).read()
+    """ocean_default_params against the s_kDefault* constants and the m_Lambda initialiser of the reference header."""
+    defaults = reference_header()["defaults"]
 
     def const(name):
-        m = re.search(r"\b%s\s*\{([^}]*)\}" % name, text)
-        assert m, name
-        return [float(x.strip().rstrip("f")) for x in m.group(1).split(",")]
+        assert name in defaults, name
+        return [float(x) for x in defaults[name]]
 
     p = abi.Params()
     abi.lib().ocean_default_params(C.byref(p))

@@ -47,8 +47,8 @@ def test_roofline_object_uses_own_bytes_and_never_exceeds_peak_on_them(bench):
 
 
 def _full_run(bench, argv=()):
-    """A fully populated run as bench.py's main() assembles it: every object the stdout line and the sidecar are built from."""
-    a = bench.parse(list(argv))
+    """A fully populated run (--full) as bench.py's main() assembles it: every object the stdout line and the sidecar are built from."""
+    a = bench.parse(["--full", *argv])
     names = ["k_zpass", "k_xpass_b", "k_xpass_disp"]
     n, tiles = a.size, a.tiles
     w = tiles * n * n / 2048 ** 2                      # (durations scaled with the work of one launch: 8 x 1024^2 is twice a 2048^2 tile)
@@ -104,6 +104,62 @@ def test_stdout_line_is_compact_strict_json_and_the_rest_goes_to_the_sidecar(ben
     # an oversized line is a bug of the script, not something to emit
     with pytest.raises(RuntimeError):
         bench.encode_line(dict(line, junk="j" * 9000))
+
+
+def test_plain_run_line_carries_the_headline_alone(bench):
+    """A plain run (no --full) measures the headline only: its line keeps every contract key, null for what --full measures, and names
+    no sidecar (none is written)."""
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and bench.parse(["--full", "--dump-outputs", "d"]).full is True
+    line = bench.build_line(a, 1, a.size, a.tiles, 2e4, 0.05, None, None, None, None, None, "a5cbb90d78459412")
+    back = json.loads(bench.encode_line(line))
+    for key in line_schema.CONTRACT_KEYS:
+        assert key in back, key
+    assert back["steps"] == 20 and back["warmup"] == 5 and back["ms_per_step"] == 0.05 and back["value"] == 2e4
+    assert back["unit"] == "frames/s" and back["higher_is_better"] is True and back["dtype"] == "f32"
+    assert back["roofline"] is None and back["cpu_baseline"] is None and back["gather"] is None and back["timing"] is None
+    assert back["sidecar"] is None
+
+
+class _FakeBatch:
+    """What bench.dump_outputs reads of an OceanBatch: read_maps(), heights(i), tiles."""
+
+    def __init__(self, n, tiles):
+        import numpy as np
+        rng = np.random.default_rng(n + tiles)
+        self.tiles = tiles
+        self.d = rng.standard_normal((tiles, n, n, 4), dtype=np.float32)
+        self.q = rng.standard_normal((tiles, n, n, 4), dtype=np.float32)
+
+    def read_maps(self):
+        return self.d.copy(), self.q.copy()
+
+    def heights(self, i):
+        return 1.5 + i, -2.25 - i, 3.0 + i
+
+
+@pytest.mark.parametrize("n,tiles", [(64, 2), (1024, 1), (2048, 1)])
+def test_dump_outputs_writes_the_maps_or_a_fixed_sample_of_them(bench, tmp_path, n, tiles):
+    """--dump-outputs: float32 / float64 .npy files, at most 64 MB in all; whole maps up to DUMP_TEXELS_MAX texels, above that the same
+    seeded sample of texels in every run."""
+    import numpy as np
+    b = _FakeBatch(n, tiles)
+    names = bench.dump_outputs(b, str(tmp_path / "a"))
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in names)
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert np.array_equal(got["heights"], np.array([b.heights(i) for i in range(tiles)], dtype=np.float32))
+    texels = tiles * n * n
+    if texels <= bench.DUMP_TEXELS_MAX:
+        assert set(names) == {"displacement", "normal", "heights"}
+        assert np.array_equal(got["displacement"], b.d) and np.array_equal(got["normal"], b.q)
+        return
+    assert set(names) == {"displacement", "normal", "heights", "sample_index"}
+    idx = got["sample_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_TEXELS_MAX and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < texels
+    assert np.array_equal(got["displacement"], b.d.reshape(-1, 4)[idx]) and np.array_equal(got["normal"], b.q.reshape(-1, 4)[idx])
+    bench.dump_outputs(b, str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "sample_index.npy"), got["sample_index"])
 
 
 def test_multi_gpu_line_carries_config5_workload_cpu_baseline_and_roofline(bench):
@@ -172,9 +228,9 @@ def test_cpu_baseline_leg_runs_and_reports_its_shape(bench):
 
 
 def test_timed_regions_are_repeated_and_reported_as_median_with_spread(bench):
-    """SURVEY.md 8d / VERDICT r03 #4: the timed region of --steps frames is repeated K >= 7 times inside one invocation; ms_per_step is the
-    median region, p10 / p90 stand beside it.  (The GPU side is exercised by tests/test_parity_bench_regimes.py; here: the defaults and
-    that the line keeps the contract's keys with the statistics added.)"""
+    """SURVEY.md 8d / VERDICT r03 #4: with --full the timed region of --steps frames is repeated K >= 7 more times inside one invocation;
+    their median, p10 / p90 stand beside ms_per_step (the headline region).  (The GPU side is exercised by tests/test_parity_bench_regimes.py;
+    here: the defaults and that the line keeps the contract's keys with the statistics added.)"""
     a = bench.parse([])
     assert a.regions >= 7
     assert bench.parse(["--regions", "11"]).regions == 11

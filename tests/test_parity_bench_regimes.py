@@ -300,7 +300,7 @@ def test_bench_self_launcher_starts_n_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["OCEAN_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--prewarm", "20",
-                        "--size", "512", "--tiles", "2", "--depth", "2", "--no-extra", "--cpu-seconds", "0.4", "--no-gather"],
+                        "--size", "512", "--tiles", "2", "--depth", "2", "--full", "--no-extra", "--cpu-seconds", "0.4", "--no-gather"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -316,6 +316,35 @@ def test_bench_self_launcher_starts_n_ranks():
     assert len(lines[0]) < 8192 and out["sidecar"] == "bench_extra.json"
     side = json.load(open(os.path.join(root, out["sidecar"])))
     assert side["line"] == out and side["warmup_frames_effective"] == 25 and side["roofline"]["kernels"]
+
+
+def test_plain_bench_run_dumps_the_last_timed_frame(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the line carries the headline alone, and DIR holds the last timed
+    step's maps (a seeded sample of them at 2048^2) and heights, bit for bit those of a serial context computing the same frame."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 20, 5
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--prewarm", "20", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["warmup"] == warmup and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(1e3 / out["ms_per_step"], rel=1e-4) and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["gather"] is None and out["sidecar"] is None
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(got) == {"displacement", "normal", "heights", "sample_index"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    ref = make_batch(2048)
+    ref.compute_waves(0.05 * (warmup + steps - 1))                 # bench.py's t of its last timed step
+    d, q = ref.read_maps()
+    idx = got["sample_index"].astype(np.int64)
+    assert np.array_equal(got["displacement"], d.reshape(-1, 4)[idx]) and np.array_equal(got["normal"], q.reshape(-1, 4)[idx])
+    assert np.array_equal(got["heights"], np.array([ref.heights(0)], dtype=np.float32))
+    ref.close()
 
 
 def test_readout_paths_under_pipelining_refer_to_the_last_frame():

@@ -42,7 +42,7 @@ def test_bench_two_gpus_over_rccl():
     if _gpus() < 2:
         pytest.skip("needs 2 GPUs")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "200", "--warmup", "50", "--prewarm", "100",
-                        "--no-extra", "--cpu-seconds", "1"], capture_output=True, text=True, env=_env(), timeout=900)
+                        "--full", "--no-extra", "--cpu-seconds", "1"], capture_output=True, text=True, env=_env(), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]          # a gather that fails or hangs exits non-zero (bench.py: give_up / failed)
     out = line_schema.last_json_line(r.stdout)
     # (the keys checked here are the ones tests/test_bench_contract.py checks on a synthetic world-8 line: one schema, tests/line_schema.py)
@@ -64,7 +64,7 @@ def test_bench_config5_invocation_on_eight_gpus():
     if _gpus() < 8:
         pytest.skip("needs 8 GPUs")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--size", "1024", "--tiles", "8", "--depth", "2",
-                        "--steps", "200", "--warmup", "50", "--prewarm", "100", "--no-extra", "--cpu-seconds", "1"],
+                        "--steps", "200", "--warmup", "50", "--prewarm", "100", "--full", "--no-extra", "--cpu-seconds", "1"],
                        capture_output=True, text=True, env=_env(), timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     out = line_schema.last_json_line(r.stdout)
