@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "ocean.h"
+#include "ocean_consumers.h"
 
 #if defined(__has_include)
 #if __has_include(<glm/glm.hpp>)
@@ -205,6 +206,26 @@ public:
 
     // Beyond the reference: the device-resident maps (no host copy), for interop.
     ocean_t* Context() const { return m_Ctx; }
+
+    // Beyond the reference: surface query (ocean_query_surface) -- the displaced position and normal of the water above each world
+    // point (x, z) = (xz[i].x, xz[i].y), for the maps of the last ComputeWaves, on the reference mesh's geometry: grid = tile size,
+    // vertex distance = s_kDefaultTileLength / s_kDefaultTileSize (WaterSurfaceMesh.h:200-202), choppy = GetDisplacementLambda().
+    // positions[i] = (x, height, z, smallest Jacobian slot), normals[i] = (unit normal, residual |P.xz - q| in metres).
+    void QuerySurface(const std::vector<vec2>& xz, std::vector<vec4>& positions, std::vector<vec4>& normals, uint32_t iterations = 8)
+    {
+        static_assert(sizeof(vec2) == 8, "points are (x, z) float pairs");
+        ocean_surface s{};
+        s.first_tile = 0; s.cascades = 1;
+        s.grid_size = ocean_tile_size(m_Ctx);
+        s.vertex_distance = s_kDefaultTileLength / (float)s_kDefaultTileSize;
+        s.choppy = GetDisplacementLambda();
+        s.iterations = iterations;
+        s.uv_scales[0] = 1.0f;
+        positions.resize(xz.size());
+        normals.resize(xz.size());
+        Check(ocean_query_surface(m_Ctx, &s, reinterpret_cast<const float*>(xz.data()), (uint32_t)xz.size(),
+                                  reinterpret_cast<float*>(positions.data()), reinterpret_cast<float*>(normals.data())), "ocean_query_surface");
+    }
 
 private:
     bool Pin(int i)

@@ -52,6 +52,49 @@ int ocean_build_mips(ocean_t* ctx, uint32_t tile);
 int ocean_read_mips(ocean_t* ctx, float* disp_mips, float* nrm_mips);
 int ocean_device_mips(ocean_t* ctx, void** d_disp_mips, void** d_nrm_mips, uint32_t* levels);
 
+/* ---- surface query: displaced height and normal at arbitrary points --------------------------------------------------
+ * What gameplay / physics code asks of an ocean (buoys, boats, cameras kept above the water): how high is the water at
+ * world point (x, z), and which way does it face.  The surface is the one ocean_displace_grid_cascades draws (one tile:
+ * cascades = 1, the surface of ocean_displace_grid).  A rest point r = (x, z) in mesh coordinates has
+ *   u = (x / vertex_distance + grid_size/2) / grid_size,  v = (z / vertex_distance + grid_size/2) / grid_size
+ * (grid_size/2 an integer division; at grid vertex (xi, yi) this is the vertex's uv); tile c of the set is sampled at
+ * (u, v) * uv_scales[c] (LINEAR, REPEAT) and
+ *   P(r) = (r.x + sum_c D_c.x,  sum_c D_c.y * A_c,  r.z + sum_c D_c.z),  w = min_c D_c.w,  n(r) = the vertex stage's normal,
+ * exactly what the vertex stage writes for a vertex at rest point r.  The water above rest point r sits at P(r).xz, not at
+ * r, so a query point q = (qx, qz) asks for the r with P(r).xz = q.  It is solved for with a diagonal Newton iteration:
+ *   r_0 = q;  for k < K:  e = P(r_k).xz - q
+ *                         Jx = 1 + sum_c lambda_c * N_c.z * s_c * L_c / (grid_size * vertex_distance)   (N_c: normal-map sample
+ *                         Jz = 1 + sum_c lambda_c * N_c.w * s_c * L_c / (grid_size * vertex_distance)    of tile c at r_k)
+ *                         J = sign(J) * 0.1 where |J| < 0.1 (J == 0 -> +0.1);  r_{k+1} = r_k - (e.x / Jx, e.z / Jz)
+ *   out_pos = (P.x, P.y, P.z, w) at r_K,   out_nrm = (n.x, n.y, n.z, |P(r_K).xz - q|)
+ * The normal map's z / w are dDx/dx and dDz/dz in ocean metres and D.x carries lambda, so J is the diagonal of dP.xz/dr.
+ * lambda_c and L_c are the displacement lambda and tile length of the frame that wrote tile c's maps (a later
+ * ocean_set_lambda does not change the answer).  fp32 throughout, no contraction (the test suite repeats it step for step).
+ * out_nrm.w shows convergence: where the surface folds over itself (Jacobian <= 0) the inverse is not unique, and the
+ * residual says so.  K = iterations: 1 .. 32, 0 means 8.
+ * Both calls read the most recently enqueued frame (caller-bound or imported output where it is, as ocean_displace_grid)
+ * and are stream-ordered behind it like the other consumers, so the rule of ocean.h holds for them unchanged: a query
+ * behind a frame whose in-launch wait gave up gets OCEAN_E_HIP once.
+ * ocean_query_surface: host arrays xz[2*points], out_pos[4*points], out_nrm[4*points], staged through a device buffer
+ * of the context that grows on demand; returns when the results are in out_pos / out_nrm.
+ * ocean_query_surface_device: the same arrays in device memory of the context's device; enqueued behind the most recent
+ * frame on its stream (ocean_stream), returns at once.
+ * Errors: OCEAN_E_NOT_READY without Prepare or frame; OCEAN_E_INVALID for cascades 0 or > 8, a tile range outside the
+ * batch, grid_size 0, iterations > 32, a NULL pointer with points > 0.  points == 0 does nothing and returns OCEAN_OK.
+ * (An addition to ABI version 5: nothing of the existing entry points or structures changes.)                         */
+typedef struct ocean_surface {
+    uint32_t first_tile, cascades;     /* 1 .. 8 tiles of the batch, as ocean_displace_grid_cascades */
+    uint32_t grid_size;                /* as ocean_displace_grid */
+    float    vertex_distance, choppy;
+    uint32_t iterations;               /* 0 = 8; at most 32 */
+    float    uv_scales[8];             /* first `cascades` used */
+} ocean_surface;
+
+int ocean_query_surface(ocean_t* ctx, const ocean_surface* s, const float* xz, uint32_t points,
+                        float* out_pos, float* out_nrm);
+int ocean_query_surface_device(ocean_t* ctx, const ocean_surface* s, const void* d_xz, uint32_t points,
+                               void* d_out_pos, void* d_out_nrm);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,42 @@ class OceanBatch:
         _abi.check(self._L.ocean_read_grid(self._h, pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)), "ocean_read_grid")
         return pos, nrm
 
+    def _surface(self, first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations) -> "_abi.Surface":
+        sc = [float(x) for x in np.atleast_1d(np.asarray(uv_scales, dtype=np.float32))]
+        if not 1 <= len(sc) <= 8:
+            raise ValueError("uv_scales: 1 .. 8 cascades")
+        s = _abi.Surface()
+        s.first_tile, s.cascades = int(first_tile), len(sc)
+        s.grid_size = self.tile_size if grid_size is None else int(grid_size)
+        s.vertex_distance = (1000.0 / 512.0) if vertex_distance is None else float(vertex_distance)
+        s.choppy, s.iterations = float(choppy), int(iterations)
+        for i, x in enumerate(sc):
+            s.uv_scales[i] = x
+        return s
+
+    def query_surface(self, xz, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                      vertex_distance: Optional[float] = None, choppy: float = -1.0, iterations: int = 8):
+        """Surface query (ocean_query_surface) on the most recent frame: the displaced position and normal of the surface the
+        vertex stage draws (tiles first_tile .. first_tile+len(uv_scales)-1 as cascades) above each world point xz [points, 2].
+        Returns (pos, nrm), each (points, 4) float32: pos = (x, height, z, smallest Jacobian slot), nrm = (unit normal, residual
+        |P.xz - xz| in metres).  Defaults as displace_grid."""
+        q = np.ascontiguousarray(xz, dtype=np.float32).reshape(-1, 2)
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        pos = np.empty((q.shape[0], 4), dtype=np.float32)
+        nrm = np.empty_like(pos)
+        _abi.check(self._L.ocean_query_surface(self._h, C.byref(s), q.ctypes.data_as(C.c_void_p), q.shape[0],
+                                               pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)), "ocean_query_surface")
+        return pos, nrm
+
+    def query_surface_device(self, d_xz: int, points: int, d_pos: int, d_nrm: int, first_tile: int = 0, uv_scales=(1.0,),
+                             grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0,
+                             iterations: int = 8):
+        """query_surface on device arrays of the context's device (ocean_query_surface_device; e.g. torch tensors' data_ptr()):
+        d_xz [points][2], d_pos / d_nrm [points][4] float32.  Enqueued on the frame's stream (`stream`); returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        _abi.check(self._L.ocean_query_surface_device(self._h, C.byref(s), C.c_void_p(d_xz), int(points), C.c_void_p(d_pos),
+                                                      C.c_void_p(d_nrm)), "ocean_query_surface_device")
+
     def build_mips(self, tile: int = 0):
         """Mip chain of both maps of `tile` (ocean_build_mips: the reference's s_kUseMipMapping path, Texture2D.cpp:228-330):
         returns (disp_levels, nrm_levels), lists of (N >> l, N >> l, 4) float32 arrays for l = 1 .. log2 N."""
@@ -513,3 +549,20 @@ class WSTessendorf:
     def SetPhillipsConst(self, A: float): self._b.set_params(phillips_const=A)
     def SetLambda(self, lam: float): self._b.set_lambda(lam)
     def SetDamping(self, damping: float): self._b.set_params(damping=damping)
+
+    # -- beyond the reference: surface query (include/WSTessendorf.hpp: QuerySurface) -----------------------------------
+    def QuerySurface(self, xz, positions: np.ndarray | None = None, normals: np.ndarray | None = None, iterations: int = 8):
+        """Displaced position and normal of the water above each world point xz [points, 2] (ocean_query_surface), for the maps of the
+        last ComputeWaves on the reference mesh's geometry: grid = tile size, vertex distance = s_kDefaultTileLength /
+        s_kDefaultTileSize (WaterSurfaceMesh.h:200-202), choppy = GetDisplacementLambda().  Fills positions / normals [points, 4]
+        float32 when given, and returns them."""
+        pos, nrm = self._b.query_surface(xz, grid_size=self._b.tile_size,
+                                         vertex_distance=self.s_kDefaultTileLength / self.s_kDefaultTileSize,
+                                         choppy=self.GetDisplacementLambda(), iterations=iterations)
+        if positions is not None:
+            positions[...] = pos.reshape(positions.shape)
+            pos = positions
+        if normals is not None:
+            normals[...] = nrm.reshape(normals.shape)
+            nrm = normals
+        return pos, nrm

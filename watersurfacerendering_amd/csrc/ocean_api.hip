@@ -69,6 +69,8 @@ static void free_device(ocean_ctx* c)
     c->k1d = nullptr; c->tw = nullptr;
     c->toff = nullptr; c->lambda = nullptr; c->tparams = nullptr; c->xi = nullptr;
     c->h0h = nullptr; c->h0_inv_scale = nullptr; c->h0_maxbits = nullptr; c->zscale = nullptr; c->zbounds = nullptr;
+    if (c->query_buf) (void)hipFree(c->query_buf);
+    c->query_buf = nullptr; c->query_capacity = 0;
     c->prepared = false; c->placement_done = false;
     // nothing of the old buffers may be referred to any more: no frame, no chain to read out, no mips of the old size
     c->have_frame = false; c->last_set = 0; c->frame_ctr = 0; c->mips_ready = false; c->grid_vertices = 0;
@@ -520,6 +522,8 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
         if (w16_env && atoi(w16_env) == 0) c->omega16 = false;
 #endif
     }
+    c->prep_length.resize(t);
+    for (size_t i = 0; i < t; ++i) c->prep_length[i] = tp[i].length;
     c->seed = seed;
     c->prepared = true;
     c->have_frame = false;
@@ -681,6 +685,8 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     }
     c->frame_valid[set] = true;
     c->tracked[set] = track;
+    c->set_lambda[set].resize(c->tiles); c->set_length[set].resize(c->tiles);
+    for (uint32_t i = 0; i < c->tiles; ++i) { c->set_lambda[set][i] = c->params[i].lambda; c->set_length[set][i] = c->prep_length[i]; }
     c->last_t[set] = t; c->last_pipe[set] = pipelined; c->last_handoff[set] = c->handoff;
     if (pipe && !redo) c->frame_ctr++;
     c->have_frame = true;
@@ -1339,6 +1345,99 @@ int ocean_device_mips(ocean_t* c, void** d_disp_mips, void** d_nrm_mips, uint32_
     if (d_disp_mips) *d_disp_mips = c->mips_ready ? c->mips_disp : nullptr;
     if (d_nrm_mips) *d_nrm_mips = c->mips_ready ? c->mips_nrm : nullptr;
     if (levels) { uint32_t l = 0; for (uint32_t w = c->mips_n; c->mips_ready && w > 1; w /= 2) ++l; *levels = l; }
+    return OCEAN_OK;
+}
+
+}  // extern "C"
+
+// Checks and launch arguments shared by the two surface queries (the device pointers are filled in by the caller).
+static int query_args(ocean_ctx* c, const ocean_surface* s, QueryArgs& a)
+{
+    if (!c || !s || s->cascades == 0 || s->cascades > (uint32_t)OCEAN_MAX_CASCADES || s->first_tile >= c->tiles ||
+        s->cascades > c->tiles - s->first_tile || s->grid_size == 0 || s->iterations > 32)
+        return OCEAN_E_INVALID;
+    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
+    const int set = c->last_set;
+    const size_t n2 = (size_t)c->n * c->n;
+    a.disp = (c->ext_disp ? c->ext_disp : c->dispN[set]) + s->first_tile * n2;
+    a.nrm = (c->ext_nrm ? c->ext_nrm : c->nrmN[set]) + s->first_tile * n2;
+    a.minmax = c->minmax[set] + 2 * s->first_tile;
+    a.tile_texels = n2;
+    a.n = (int)c->n;
+    a.count = (int)s->cascades;
+    a.iterations = s->iterations ? (int)s->iterations : 8;
+    a.grid = (float)s->grid_size;
+    a.half = (float)(s->grid_size / 2);
+    a.vertex_distance = s->vertex_distance;
+    a.choppy = s->choppy;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) {
+        a.uv_scale[i] = i < s->cascades ? s->uv_scales[i] : 0.0f;
+        a.gain[i] = 0.0f;
+        if (i < s->cascades) {      // lambda_c * (s_c * L_c / (grid * vertex_distance)) of the frame that wrote tile c's maps
+            const uint32_t tile = s->first_tile + i;
+            a.gain[i] = c->set_lambda[set][tile] * (s->uv_scales[i] * c->set_length[set][tile] / (a.grid * s->vertex_distance));
+        }
+    }
+    return OCEAN_OK;
+}
+
+static int launch_query(ocean_ctx* c, const QueryArgs& a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_query_surface, dim3((a.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_query_surface(ocean_t* c, const ocean_surface* s, const float* xz, uint32_t points, float* out_pos, float* out_nrm)
+{
+    QueryArgs a;
+    { int rc_ = query_args(c, s, a); if (rc_) return rc_; }
+    if (points == 0) return OCEAN_OK;
+    if (!xz || !out_pos || !out_nrm) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    if (points > c->query_capacity) {
+        SYNC_ALL(c);
+        if (c->query_buf) (void)hipFree(c->query_buf);
+        c->query_buf = nullptr; c->query_capacity = 0;
+        HIP_TRY(hipMalloc(&c->query_buf, (size_t)points * 10 * sizeof(float)));
+        c->query_capacity = points;
+    }
+    // [positions | normals | points]: the float4 arrays first, so that every array is 16-byte aligned
+    float* d_pos = c->query_buf;
+    float* d_nrm = d_pos + (size_t)points * 4;
+    float* d_xz = d_nrm + (size_t)points * 4;
+    a.xz = reinterpret_cast<const float2*>(d_xz);
+    a.out_pos = reinterpret_cast<float4*>(d_pos);
+    a.out_nrm = reinterpret_cast<float4*>(d_nrm);
+    a.points = points;
+    hipStream_t st = stream_of(c, c->last_set);             // ordered after the frame that wrote these maps
+    CONSUMER_BEGIN(c, st);
+    HIP_TRY(hipMemcpyAsync(d_xz, xz, (size_t)points * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+    { int rc_ = launch_query(c, a, st); if (rc_) return rc_; }
+    HIP_TRY(hipMemcpyAsync(out_pos, d_pos, (size_t)points * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_nrm, d_nrm, (size_t)points * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    CONSUMER_END(c, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    return OCEAN_OK;
+}
+
+int ocean_query_surface_device(ocean_t* c, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out_pos, void* d_out_nrm)
+{
+    QueryArgs a;
+    { int rc_ = query_args(c, s, a); if (rc_) return rc_; }
+    if (points == 0) return OCEAN_OK;
+    if (!d_xz || !d_out_pos || !d_out_nrm) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    a.xz = static_cast<const float2*>(d_xz);
+    a.out_pos = static_cast<float4*>(d_out_pos);
+    a.out_nrm = static_cast<float4*>(d_out_nrm);
+    a.points = points;
+    hipStream_t st = stream_of(c, c->last_set);
+    CONSUMER_BEGIN(c, st);
+    { int rc_ = launch_query(c, a, st); if (rc_) return rc_; }
+    CONSUMER_END(c, st);
     return OCEAN_OK;
 }
 

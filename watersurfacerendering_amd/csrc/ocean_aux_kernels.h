@@ -313,5 +313,92 @@ __global__ void k_mip_level(const MipArgs m)
                                        mix(t00.z, t10.z, t01.z, t11.z), mix(t00.w, t10.w, t01.w, t11.w));
 }
 
+// Surface query (include/ocean_consumers.h: ocean_query_surface): the displaced height and normal of the surface the vertex stage draws
+// (k_displace_grid_cascades) at arbitrary points q = (x, z).  The water above rest point r sits at P(r).xz = r + D(r).xz, so the rest point
+// of q is solved for with a diagonal Newton iteration from r_0 = q:
+//   r_{k+1} = r_k - (P(r_k).xz - q) / J(r_k),   J = 1 + sum_c gain_c * (nrm_c.z, nrm_c.w),   |J| clamped to >= 0.1 (sign kept, 0 -> +0.1)
+// gain_c = lambda_c * (s_c * L_c / (grid * vertex_distance)) (host-computed): the normal map's z / w hold dDx/dx, dDz/dz in ocean metres,
+// one mesh metre is s_c * L_c / (grid * vertex_distance) ocean metres of tile c, and disp.x carries lambda.  P, the normal and
+// w = min_c D_c.w are then evaluated at r_K exactly as the cascade vertex stage would for a vertex at r_K; out_nrm.w = |P(r_K).xz - q|.
+// One thread per point; K + 1 evaluations of 2 bilinear float4 gathers per cascade, all in fp32 in the order written below (no
+// contraction), which tests/surface_query.py repeats step for step.
+struct QueryArgs {
+    const float4* disp;                // maps of the FIRST tile of the cascade set (tile c at + c * tile_texels)
+    const float4* nrm;
+    const unsigned* minmax;            // height keys of the first tile (2 per tile)
+    const float2* xz;                  // [points]
+    float4* out_pos;                   // [points]  (P.x, P.y, P.z, min_c D_c.w)
+    float4* out_nrm;                   // [points]  (n.x, n.y, n.z, residual)
+    size_t tile_texels;                // N * N
+    unsigned points;
+    int n;                             // map size
+    int count;                         // cascades, 1 .. OCEAN_MAX_CASCADES
+    int iterations;                    // K, 1 .. 32
+    float grid;                        // grid_size
+    float half;                        // grid_size / 2 (integer division, as the vertex stage's centring)
+    float vertex_distance;
+    float choppy;
+    float uv_scale[OCEAN_MAX_CASCADES];
+    float gain[OCEAN_MAX_CASCADES];
+};
+
+struct SurfaceEval {
+    float dx, dy, dz, w;               // summed displacement (heights times their amplitude), smallest Jacobian slot
+    float sx, sz, ddx, ddz;            // summed normal-map samples
+    float jx, jz;                      // sum_c gain_c * (nrm_c.z, nrm_c.w)
+};
+
+__device__ __forceinline__ SurfaceEval eval_surface(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float rx, float rz)
+{
+#pragma clang fp contract(off)
+    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
+    SurfaceEval e{0.0f, 0.0f, 0.0f, 3.402823466e+38f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) {
+        if (c >= a.count) break;
+        const float us = u * a.uv_scale[c], vs = v * a.uv_scale[c];
+        const float4 d = sample_linear_repeat(a.disp + (size_t)c * a.tile_texels, a.n, us, vs);
+        const float4 sl = sample_linear_repeat(a.nrm + (size_t)c * a.tile_texels, a.n, us, vs);
+        e.dx = e.dx + d.x; e.dy = e.dy + d.y * amp[c]; e.dz = e.dz + d.z;
+        e.w = fminf(e.w, d.w);
+        e.sx = e.sx + sl.x; e.sz = e.sz + sl.y; e.ddx = e.ddx + sl.z; e.ddz = e.ddz + sl.w;
+        e.jx = e.jx + sl.z * a.gain[c]; e.jz = e.jz + sl.w * a.gain[c];
+    }
+    return e;
+}
+
+__device__ __forceinline__ float clamp_jacobian(float j)
+{
+    return fabsf(j) < 0.1f ? (j < 0.0f ? -0.1f : 0.1f) : j;
+}
+
+__global__ void __launch_bounds__(256) k_query_surface(const QueryArgs a)
+{
+#pragma clang fp contract(off)
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.points) return;
+    float amp[OCEAN_MAX_CASCADES];
+#pragma unroll
+    for (int c = 0; c < OCEAN_MAX_CASCADES; ++c)
+        amp[c] = c < a.count ? fmaxf(fabsf(key_float(a.minmax[2 * c + 0])), fabsf(key_float(a.minmax[2 * c + 1]))) : 0.0f;
+    const float2 q = a.xz[i];
+    float rx = q.x, rz = q.y;
+    for (int k = 0; k < a.iterations; ++k) {
+        const SurfaceEval e = eval_surface(a, amp, rx, rz);
+        const float ex = (rx + e.dx) - q.x, ez = (rz + e.dz) - q.y;
+        const float jx = clamp_jacobian(1.0f + e.jx), jz = clamp_jacobian(1.0f + e.jz);
+        rx = rx - ex / jx;
+        rz = rz - ez / jz;
+    }
+    const SurfaceEval e = eval_surface(a, amp, rx, rz);
+    const float px = rx + e.dx, pz = rz + e.dz;
+    const float ex = px - q.x, ez = pz - q.y;
+    a.out_pos[i] = make_float4(px, 0.0f + e.dy, pz, e.w);
+    const float nx = -(e.sx / (1.0f + a.choppy * e.ddx));
+    const float nz = -(e.sz / (1.0f + a.choppy * e.ddz));
+    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
+    a.out_nrm[i] = make_float4(nx / len, 1.0f / len, nz / len, sqrtf(ex * ex + ez * ez));
+}
+
 
 }  // namespace ocean

@@ -182,6 +182,11 @@ struct ocean_ctx {
     float4* mips_nrm = nullptr;
     uint32_t mips_n = 0;            // tile size the two buffers were allocated for
     bool mips_ready = false;
+    std::vector<float> prep_length;         // [tiles] tile length the most recent ocean_prepare built the spectrum for
+    std::vector<float> set_lambda[MAXD];    // [tiles] lambda and tile length of the frame that wrote each chain's maps
+    std::vector<float> set_length[MAXD];    //   (recorded when it is enqueued: what ocean_query_surface's Newton step needs)
+    float* query_buf = nullptr;     // ocean_query_surface: staging of the points and results, 10 floats per point (grows on demand)
+    uint32_t query_capacity = 0;    // points it holds
     unsigned long long* stamps = nullptr;   // diagnostic builds only
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
