@@ -43,6 +43,7 @@
 #ifndef WS_TESSENDORF_HAVE_GLM
 namespace wsvec {
 struct vec2 { float x, y; vec2(float a = 0.f, float b = 0.f) : x(a), y(b) {} };
+struct vec3 { float x, y, z; vec3(float a = 0.f, float b = 0.f, float c = 0.f) : x(a), y(b), z(c) {} };
 struct vec4 { float x, y, z, w; vec4(float a = 0.f, float b = 0.f, float c = 0.f, float d = 0.f) : x(a), y(b), z(c), w(d) {} };
 }  // namespace wsvec
 #endif
@@ -52,9 +53,11 @@ class WSTessendorf
 public:
 #ifdef WS_TESSENDORF_HAVE_GLM
     using vec2 = glm::vec2;
+    using vec3 = glm::vec3;
     using vec4 = glm::vec4;
 #else
     using vec2 = wsvec::vec2;
+    using vec3 = wsvec::vec3;
     using vec4 = wsvec::vec4;
 #endif
     static constexpr uint32_t s_kDefaultTileSize{ 512 };
@@ -225,6 +228,36 @@ public:
         normals.resize(xz.size());
         Check(ocean_query_surface(m_Ctx, &s, reinterpret_cast<const float*>(xz.data()), (uint32_t)xz.size(),
                                   reinterpret_cast<float*>(positions.data()), reinterpret_cast<float*>(normals.data())), "ocean_query_surface");
+    }
+
+    // Beyond the reference: ray cast (ocean_raycast_surface) -- where each ray origins[i] + t * directions[i] first meets the water of
+    // QuerySurface (same geometry) within max_distance metres.  hits[i] = (x, height, z, t), or (x, height, z, -2) and a depth for an
+    // origin under water, or (0, 0, 0, -1) for a miss; normals[i] = (unit normal, signed gap at the hit or the depth, <= 0).
+    // steps: coarse samples across the height slab (0 = 64), refine: rounds of 16-part splits (0 = 3).
+    void RaycastSurface(const std::vector<vec3>& origins, const std::vector<vec3>& directions, float max_distance,
+                        std::vector<vec4>& hits, std::vector<vec4>& normals, uint32_t steps = 0, uint32_t refine = 0,
+                        uint32_t iterations = 8)
+    {
+        static_assert(sizeof(vec3) == 12, "origins and directions are float triples");
+        if (origins.size() != directions.size()) throw std::runtime_error("RaycastSurface: origins and directions differ in size");
+        ocean_surface s{};
+        s.first_tile = 0; s.cascades = 1;
+        s.grid_size = ocean_tile_size(m_Ctx);
+        s.vertex_distance = s_kDefaultTileLength / (float)s_kDefaultTileSize;
+        s.choppy = GetDisplacementLambda();
+        s.iterations = iterations;
+        s.uv_scales[0] = 1.0f;
+        ocean_raycast r{};
+        r.max_distance = max_distance; r.steps = steps; r.refine = refine;
+        std::vector<float> rays(origins.size() * 6);
+        for (size_t i = 0; i < origins.size(); ++i) {
+            rays[6 * i + 0] = origins[i].x; rays[6 * i + 1] = origins[i].y; rays[6 * i + 2] = origins[i].z;
+            rays[6 * i + 3] = directions[i].x; rays[6 * i + 4] = directions[i].y; rays[6 * i + 5] = directions[i].z;
+        }
+        hits.resize(origins.size());
+        normals.resize(origins.size());
+        Check(ocean_raycast_surface(m_Ctx, &s, &r, rays.data(), (uint32_t)origins.size(),
+                                    reinterpret_cast<float*>(hits.data()), reinterpret_cast<float*>(normals.data())), "ocean_raycast_surface");
     }
 
 private:

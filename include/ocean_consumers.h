@@ -95,6 +95,52 @@ int ocean_query_surface(ocean_t* ctx, const ocean_surface* s, const float* xz, u
 int ocean_query_surface_device(ocean_t* ctx, const ocean_surface* s, const void* d_xz, uint32_t points,
                                void* d_out_pos, void* d_out_nrm);
 
+/* ---- ray cast: where a ray first meets the water --------------------------------------------------------------------
+ * Camera picking, projectiles and splashes, line of sight over the waves, a camera's near plane kept out of a crest, "is the
+ * camera under water?".  The surface is exactly the one ocean_query_surface defines for the same ocean_surface (tiles,
+ * cascades, grid, vertex distance, choppiness, Newton iterations K): write H(x, z) for the out_pos.y that query returns at
+ * (x, z).  fp32 throughout, no contraction, in this order (the test suite repeats it step for step):
+ *   Direction   len = sqrtf((dx*dx + dy*dy) + dz*dz); a zero or non-finite len is a miss; d = (dx/len, dy/len, dz/len).
+ *   Gap         p(t) = (o.x + t*d.x, o.y + t*d.y, o.z + t*d.z),  f(t) = p(t).y - H(p(t).x, p(t).z): the height above the water.
+ *   Slab        Hmax = 1.001f * (amp_0 + amp_1 + ...) (sum from 0.0f in cascade order; amp_c is the largest magnitude of tile
+ *               c's height keys, the amplitude the query scales heights with), so every height lies in [-Hmax, Hmax].
+ *               If o.y <= -Hmax the origin is under water (below).  Otherwise [0, max_distance] is clipped to the slab:
+ *                 d.y < 0:   t0 = fmaxf(0, (Hmax - o.y) / d.y),   t1 = fminf(max_distance, (-Hmax - o.y) / d.y)
+ *                 d.y > 0:   t0 = fmaxf(0, (-Hmax - o.y) / d.y),  t1 = fminf(max_distance, (Hmax - o.y) / d.y)
+ *                 d.y == 0:  t0 = 0, t1 = max_distance if o.y < Hmax; otherwise the segment is empty
+ *               and the segment is empty where t1 < t0: a miss.
+ *   March       M = steps, h = (t1 - t0) / (float)M, samples t_i = t0 + (float)i * h for i = 0 .. M with t_M := t1.  The first i
+ *               with f(t_i) <= 0 decides; none is a miss.  i == 0: if t0 == 0 the origin is under water, otherwise the hit is at
+ *               t = t0.  Else the bracket is [a, b] = [t_{i-1}, t_i] with f(a) > 0 >= f(b).
+ *   Refinement  R = refine rounds; each has s_j = a + (float)j * ((b - a) / 16.0f) for j = 1 .. 15 and s_16 := b, s_0 := a: the
+ *               first j with f(s_j) <= 0 gives [a, b] := [s_{j-1}, s_j] (f known at both ends already).
+ *   Hit         t = a + (b - a) * (fa / (fa - fb)) (fa = f(a), fb = f(b)), then one query at (p(t).x, p(t).z):
+ *                 out_hit = (P.x, P.y, P.z, t),  out_nrm = (query normal, p(t).y - P.y)   (P.y is the water height there;
+ *                 out_nrm.w, the signed gap at the hit, is ~ 0)
+ *   Under water out_hit = (P.x, P.y, P.z, -2),  out_nrm = (query normal, o.y - P.y)  with P the query at (o.x, o.z): the depth, <= 0
+ *   Miss        out_hit = (0, 0, 0, -1),  out_nrm = (0, 0, 0, 0)
+ * Not covered: rays that start under water and look for the surface from below get only the depth; where the surface folds
+ * (Jacobian <= 0) the height field the query defines is not unique (its residual shows it), and the ray meets that height
+ * field, not the folded sheet; a wet interval thinner than one coarse step can be stepped over (raise steps).
+ * Both calls read the most recently enqueued frame (caller-bound or imported output where it is) and are stream-ordered
+ * behind it like ocean_query_surface.  ocean_raycast_surface: host arrays rays[6*count] (ox, oy, oz, dx, dy, dz),
+ * out_hit[4*count], out_nrm[4*count], staged through a device buffer of the context that grows on demand; returns when the
+ * results are there.  ocean_raycast_surface_device: the same arrays in device memory of the context's device (rays 4-byte,
+ * outputs 16-byte aligned); enqueued behind the most recent frame on its stream (ocean_stream), returns at once.
+ * Errors: OCEAN_E_NOT_READY without Prepare or frame; OCEAN_E_INVALID for a NULL s or r, the invalid ocean_surface cases of
+ * ocean_query_surface, a max_distance <= 0 or not finite, steps > 4096, refine > 8, a NULL array with count > 0.
+ * count == 0 does nothing and returns OCEAN_OK.  (An addition to ABI version 5.)                                         */
+typedef struct ocean_raycast {
+    float    max_distance;             /* > 0 and finite: rays cover t in [0, max_distance] metres along the unit direction */
+    uint32_t steps;                    /* coarse samples across the part of the ray inside the height slab: 0 = 64, at most 4096 */
+    uint32_t refine;                   /* refinement rounds, each splitting the bracket into 16 equal parts: 0 = 3, at most 8 */
+} ocean_raycast;
+
+int ocean_raycast_surface(ocean_t* ctx, const ocean_surface* s, const ocean_raycast* r,
+                          const float* rays, uint32_t count, float* out_hit, float* out_nrm);
+int ocean_raycast_surface_device(ocean_t* ctx, const ocean_surface* s, const ocean_raycast* r,
+                                 const void* d_rays, uint32_t count, void* d_out_hit, void* d_out_nrm);
+
 #ifdef __cplusplus
 }
 #endif

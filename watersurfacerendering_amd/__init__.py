@@ -282,6 +282,44 @@ class OceanBatch:
         _abi.check(self._L.ocean_query_surface_device(self._h, C.byref(s), C.c_void_p(d_xz), int(points), C.c_void_p(d_pos),
                                                       C.c_void_p(d_nrm)), "ocean_query_surface_device")
 
+    @staticmethod
+    def _raycast(max_distance, steps, refine) -> "_abi.Raycast":
+        r = _abi.Raycast()
+        r.max_distance, r.steps, r.refine = float(max_distance), int(steps), int(refine)
+        return r
+
+    def raycast_surface(self, origins, directions, max_distance: float, steps: int = 0, refine: int = 0, first_tile: int = 0,
+                        uv_scales=(1.0,), grid_size: Optional[int] = None, vertex_distance: Optional[float] = None,
+                        choppy: float = -1.0, iterations: int = 8):
+        """Ray cast (ocean_raycast_surface) on the most recent frame: where each ray origins[i] + t * directions[i] (both [rays, 3];
+        directions need not be unit length) first meets the surface query_surface defines, for t in [0, max_distance] metres.
+        steps (0 = 64) coarse samples over the part of the ray inside the height slab, refine (0 = 3) rounds of 16-part splits.
+        Returns (hit, nrm), each (rays, 4) float32: a hit is (x, height, z, t) and (unit normal, signed gap); an origin under water
+        gives (x, height, z, -2) and (unit normal, depth <= 0) at the origin's xz; a miss (0, 0, 0, -1) and zeros."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and directions: the same number of rays")
+        rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        r = self._raycast(max_distance, steps, refine)
+        hit = np.empty((rays.shape[0], 4), dtype=np.float32)
+        nrm = np.empty_like(hit)
+        _abi.check(self._L.ocean_raycast_surface(self._h, C.byref(s), C.byref(r), rays.ctypes.data_as(C.c_void_p), rays.shape[0],
+                                                 hit.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)), "ocean_raycast_surface")
+        return hit, nrm
+
+    def raycast_surface_device(self, d_rays: int, count: int, d_hit: int, d_nrm: int, max_distance: float, steps: int = 0,
+                               refine: int = 0, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                               vertex_distance: Optional[float] = None, choppy: float = -1.0, iterations: int = 8):
+        """raycast_surface on device arrays of the context's device (ocean_raycast_surface_device; e.g. torch tensors' data_ptr()):
+        d_rays [count][6] (ox, oy, oz, dx, dy, dz), d_hit / d_nrm [count][4] float32.  Enqueued on the frame's stream (`stream`);
+        returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        r = self._raycast(max_distance, steps, refine)
+        _abi.check(self._L.ocean_raycast_surface_device(self._h, C.byref(s), C.byref(r), C.c_void_p(d_rays), int(count),
+                                                        C.c_void_p(d_hit), C.c_void_p(d_nrm)), "ocean_raycast_surface_device")
+
     def build_mips(self, tile: int = 0):
         """Mip chain of both maps of `tile` (ocean_build_mips: the reference's s_kUseMipMapping path, Texture2D.cpp:228-330):
         returns (disp_levels, nrm_levels), lists of (N >> l, N >> l, 4) float32 arrays for l = 1 .. log2 N."""
@@ -566,3 +604,20 @@ class WSTessendorf:
             normals[...] = nrm.reshape(normals.shape)
             nrm = normals
         return pos, nrm
+
+    # -- beyond the reference: ray cast (include/WSTessendorf.hpp: RaycastSurface) ---------------------------------------
+    def RaycastSurface(self, origins, directions, max_distance: float, hits: np.ndarray | None = None, normals: np.ndarray | None = None,
+                       steps: int = 0, refine: int = 0, iterations: int = 8):
+        """Where each ray origins[i] + t * directions[i] ([rays, 3]) first meets the water within max_distance metres
+        (ocean_raycast_surface), on the geometry of QuerySurface.  Fills hits / normals [rays, 4] float32 when given, and returns
+        them: hits = (x, height, z, t; -2 for an origin under water, -1 for a miss), normals = (unit normal, signed gap or depth)."""
+        hit, nrm = self._b.raycast_surface(origins, directions, max_distance, steps, refine, grid_size=self._b.tile_size,
+                                           vertex_distance=self.s_kDefaultTileLength / self.s_kDefaultTileSize,
+                                           choppy=self.GetDisplacementLambda(), iterations=iterations)
+        if hits is not None:
+            hits[...] = hit.reshape(hits.shape)
+            hit = hits
+        if normals is not None:
+            normals[...] = nrm.reshape(normals.shape)
+            nrm = normals
+        return hit, nrm

@@ -41,7 +41,7 @@ SYMBOLS_BOUNDARY = [        # include/ocean.h: the drop-in boundary (SURVEY.md 8
 SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_displace_grid", "ocean_displace_grid_cascades", "ocean_read_grid", "ocean_device_grid",
     "ocean_mip_texels", "ocean_build_mips", "ocean_read_mips", "ocean_device_mips",
-    "ocean_query_surface", "ocean_query_surface_device",
+    "ocean_query_surface", "ocean_query_surface_device", "ocean_raycast_surface", "ocean_raycast_surface_device",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
     "ocean_read_spectrum", "ocean_read_xi",
@@ -83,6 +83,11 @@ class Surface(C.Structure):
     _fields_ = [("first_tile", C.c_uint32), ("cascades", C.c_uint32), ("grid_size", C.c_uint32),
                 ("vertex_distance", C.c_float), ("choppy", C.c_float), ("iterations", C.c_uint32),
                 ("uv_scales", C.c_float * 8)]
+
+
+class Raycast(C.Structure):
+    """struct ocean_raycast (include/ocean_consumers.h): how far and how finely a ray cast samples each ray."""
+    _fields_ = [("max_distance", C.c_float), ("steps", C.c_uint32), ("refine", C.c_uint32)]
 
 
 last_build = ""      # what the most recent build() did, for the caller to log
@@ -219,6 +224,8 @@ def lib() -> C.CDLL:
         "ocean_device_mips": (i32, [P, C.POINTER(P), C.POINTER(P), C.POINTER(u32)]),
         "ocean_query_surface": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_query_surface_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_raycast_surface": (i32, [P, C.POINTER(Surface), C.POINTER(Raycast), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_raycast_surface_device": (i32, [P, C.POINTER(Surface), C.POINTER(Raycast), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_set_mode": (i32, [P, i32]),
         "ocean_set_dispersion": (i32, [P, i32, f32]),
         "ocean_set_spectrum_precision": (i32, [P, i32]),

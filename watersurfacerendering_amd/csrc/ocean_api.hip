@@ -71,6 +71,8 @@ static void free_device(ocean_ctx* c)
     c->h0h = nullptr; c->h0_inv_scale = nullptr; c->h0_maxbits = nullptr; c->zscale = nullptr; c->zbounds = nullptr;
     if (c->query_buf) (void)hipFree(c->query_buf);
     c->query_buf = nullptr; c->query_capacity = 0;
+    if (c->ray_buf) (void)hipFree(c->ray_buf);
+    c->ray_buf = nullptr; c->ray_capacity = 0;
     c->prepared = false; c->placement_done = false;
     // nothing of the old buffers may be referred to any more: no frame, no chain to read out, no mips of the old size
     c->have_frame = false; c->last_set = 0; c->frame_ctr = 0; c->mips_ready = false; c->grid_vertices = 0;
@@ -1437,6 +1439,83 @@ int ocean_query_surface_device(ocean_t* c, const ocean_surface* s, const void* d
     hipStream_t st = stream_of(c, c->last_set);
     CONSUMER_BEGIN(c, st);
     { int rc_ = launch_query(c, a, st); if (rc_) return rc_; }
+    CONSUMER_END(c, st);
+    return OCEAN_OK;
+}
+
+}  // extern "C"
+
+// Checks and launch arguments shared by the two ray casts: the surface of the query, then the ray settings.
+static int raycast_args(ocean_ctx* c, const ocean_surface* s, const ocean_raycast* r, RaycastArgs& a)
+{
+    if (!c || !s || !r || !(r->max_distance > 0.0f) || !std::isfinite(r->max_distance) || r->steps > 4096 || r->refine > 8)
+        return OCEAN_E_INVALID;
+    { int rc_ = query_args(c, s, a.q); if (rc_) return rc_; }
+    a.max_distance = r->max_distance;
+    a.steps = r->steps ? (int)r->steps : 64;
+    a.refine = r->refine ? (int)r->refine : 3;
+    return OCEAN_OK;
+}
+
+static int launch_raycast(ocean_ctx* c, const RaycastArgs& a, hipStream_t st)
+{
+    const unsigned rays_per_block = 256u / RAYCAST_LANES;
+    hipLaunchKernelGGL(k_raycast_surface, dim3((unsigned)(((uint64_t)a.count + rays_per_block - 1u) / rays_per_block)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_raycast_surface(ocean_t* c, const ocean_surface* s, const ocean_raycast* r, const float* rays, uint32_t count,
+                          float* out_hit, float* out_nrm)
+{
+    RaycastArgs a{};
+    { int rc_ = raycast_args(c, s, r, a); if (rc_) return rc_; }
+    if (count == 0) return OCEAN_OK;
+    if (!rays || !out_hit || !out_nrm) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    if (count > c->ray_capacity) {
+        SYNC_ALL(c);
+        if (c->ray_buf) (void)hipFree(c->ray_buf);
+        c->ray_buf = nullptr; c->ray_capacity = 0;
+        HIP_TRY(hipMalloc(&c->ray_buf, (size_t)count * 14 * sizeof(float)));
+        c->ray_capacity = count;
+    }
+    // [hits | normals | rays]: the float4 arrays first, so that every array is 16-byte aligned
+    float* d_hit = c->ray_buf;
+    float* d_nrm = d_hit + (size_t)count * 4;
+    float* d_rays = d_nrm + (size_t)count * 4;
+    a.rays = d_rays;
+    a.out_hit = reinterpret_cast<float4*>(d_hit);
+    a.out_nrm = reinterpret_cast<float4*>(d_nrm);
+    a.count = count;
+    hipStream_t st = stream_of(c, c->last_set);             // ordered after the frame that wrote these maps
+    CONSUMER_BEGIN(c, st);
+    HIP_TRY(hipMemcpyAsync(d_rays, rays, (size_t)count * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+    { int rc_ = launch_raycast(c, a, st); if (rc_) return rc_; }
+    HIP_TRY(hipMemcpyAsync(out_hit, d_hit, (size_t)count * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_nrm, d_nrm, (size_t)count * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    CONSUMER_END(c, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    return OCEAN_OK;
+}
+
+int ocean_raycast_surface_device(ocean_t* c, const ocean_surface* s, const ocean_raycast* r, const void* d_rays, uint32_t count,
+                                 void* d_out_hit, void* d_out_nrm)
+{
+    RaycastArgs a{};
+    { int rc_ = raycast_args(c, s, r, a); if (rc_) return rc_; }
+    if (count == 0) return OCEAN_OK;
+    if (!d_rays || !d_out_hit || !d_out_nrm) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    a.rays = static_cast<const float*>(d_rays);
+    a.out_hit = static_cast<float4*>(d_out_hit);
+    a.out_nrm = static_cast<float4*>(d_out_nrm);
+    a.count = count;
+    hipStream_t st = stream_of(c, c->last_set);
+    CONSUMER_BEGIN(c, st);
+    { int rc_ = launch_raycast(c, a, st); if (rc_) return rc_; }
     CONSUMER_END(c, st);
     return OCEAN_OK;
 }

@@ -372,32 +372,218 @@ __device__ __forceinline__ float clamp_jacobian(float j)
     return fabsf(j) < 0.1f ? (j < 0.0f ? -0.1f : 0.1f) : j;
 }
 
-__global__ void __launch_bounds__(256) k_query_surface(const QueryArgs a)
+// Per-cascade amplitude (the height key's largest magnitude) of the cascade set, 0 beyond a.count.
+__device__ __forceinline__ void query_amplitudes(const QueryArgs& a, float (&amp)[OCEAN_MAX_CASCADES])
 {
-#pragma clang fp contract(off)
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.points) return;
-    float amp[OCEAN_MAX_CASCADES];
 #pragma unroll
     for (int c = 0; c < OCEAN_MAX_CASCADES; ++c)
         amp[c] = c < a.count ? fmaxf(fabsf(key_float(a.minmax[2 * c + 0])), fabsf(key_float(a.minmax[2 * c + 1]))) : 0.0f;
-    const float2 q = a.xz[i];
-    float rx = q.x, rz = q.y;
+}
+
+// The K Newton steps from r_0 = q: the rest point whose displaced xz is q.
+__device__ __forceinline__ void solve_rest(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float qx, float qz, float& rx, float& rz)
+{
+#pragma clang fp contract(off)
+    rx = qx; rz = qz;
     for (int k = 0; k < a.iterations; ++k) {
         const SurfaceEval e = eval_surface(a, amp, rx, rz);
-        const float ex = (rx + e.dx) - q.x, ez = (rz + e.dz) - q.y;
+        const float ex = (rx + e.dx) - qx, ez = (rz + e.dz) - qz;
         const float jx = clamp_jacobian(1.0f + e.jx), jz = clamp_jacobian(1.0f + e.jz);
         rx = rx - ex / jx;
         rz = rz - ez / jz;
     }
+}
+
+// The whole query at q: out_pos / out_nrm of ocean_query_surface.
+__device__ __forceinline__ void query_point(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float qx, float qz, float4& pos, float4& nrm)
+{
+#pragma clang fp contract(off)
+    float rx, rz;
+    solve_rest(a, amp, qx, qz, rx, rz);
     const SurfaceEval e = eval_surface(a, amp, rx, rz);
     const float px = rx + e.dx, pz = rz + e.dz;
-    const float ex = px - q.x, ez = pz - q.y;
-    a.out_pos[i] = make_float4(px, 0.0f + e.dy, pz, e.w);
+    const float ex = px - qx, ez = pz - qz;
+    pos = make_float4(px, 0.0f + e.dy, pz, e.w);
     const float nx = -(e.sx / (1.0f + a.choppy * e.ddx));
     const float nz = -(e.sz / (1.0f + a.choppy * e.ddz));
     const float len = sqrtf(nx * nx + 1.0f + nz * nz);
-    a.out_nrm[i] = make_float4(nx / len, 1.0f / len, nz / len, sqrtf(ex * ex + ez * ez));
+    nrm = make_float4(nx / len, 1.0f / len, nz / len, sqrtf(ex * ex + ez * ez));
+}
+
+// H(x, z): only the height of the query at q (out_pos.y), without the normal.
+__device__ __forceinline__ float surface_height(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float qx, float qz)
+{
+#pragma clang fp contract(off)
+    float rx, rz;
+    solve_rest(a, amp, qx, qz, rx, rz);
+    return 0.0f + eval_surface(a, amp, rx, rz).dy;
+}
+
+__global__ void __launch_bounds__(256) k_query_surface(const QueryArgs a)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.points) return;
+    float amp[OCEAN_MAX_CASCADES];
+    query_amplitudes(a, amp);
+    const float2 q = a.xz[i];
+    float4 pos, nrm;
+    query_point(a, amp, q.x, q.y, pos, nrm);
+    a.out_pos[i] = pos;
+    a.out_nrm[i] = nrm;
+}
+
+// Ray cast (include/ocean_consumers.h: ocean_raycast_surface): the first point where each ray meets the surface of the query, H(x, z).
+// The gap f(t) = p(t).y - H(p(t).xz) is sampled at M + 1 points over the part of the ray inside the height slab |y| <= Hmax; the first sample
+// with f <= 0 closes the bracket [a, b], R rounds each split it into 16 equal parts and keep the first part that ends at or under the water,
+// and the hit is the secant point of the last bracket, queried once more for its position and normal.  The header states every rule.
+//
+// A lane group of RAYCAST_LANES = 16 lanes per ray, 4 rays per wave64: one group-wide step evaluates 16 consecutive coarse samples, or the
+// 15 inner points s_1 .. s_15 of one refinement round (lane j takes sample j; lane 0 has nothing to do in a round), and a 64-bit ballot
+// of (f <= 0) with the group's 16 bits cut out gives the first such sample (its ctz).  -DOCEAN_RAYCAST_LANES=1 builds the same loop with
+// one thread per ray (one sample per step; a developer variant for tools/raycast_timing.py, DESIGN.md has the figures).  The first sample with f <= 0 does not depend on
+// the order of evaluation, so this is bit for bit the sequential definition (tests/surface_raycast.py), with a dependent chain of
+// ceil((i + 1) / 16) + R + 1 evaluations instead of i + 1 + 15 R + 1.  Every lane of the wave reaches every ballot and shuffle: a
+// group that is done (or has no ray) keeps looping with its state frozen until the wave-uniform loop ends.  fp32, no contraction.
+struct RaycastArgs {
+    QueryArgs q;                       // the surface (q.xz / out_* / points unused)
+    const float* rays;                 // [count][6] ox, oy, oz, dx, dy, dz
+    float4* out_hit;                   // [count]
+    float4* out_nrm;                   // [count]
+    unsigned count;
+    float max_distance;
+    int steps;                         // M, 1 .. 4096
+    int refine;                        // R, 0 .. 8
+};
+
+#ifndef OCEAN_RAYCAST_LANES
+#define OCEAN_RAYCAST_LANES 16
+#endif
+constexpr int RAYCAST_LANES = OCEAN_RAYCAST_LANES;
+static_assert(RAYCAST_LANES >= 1 && 16 % RAYCAST_LANES == 0, "a lane group divides 16");
+// first j of a round's first step: the steps of a round then end exactly at s_15 (0 for 2..16 lanes, 1 for one lane)
+constexpr int RAYCAST_J0 = 16 - RAYCAST_LANES * ((15 + RAYCAST_LANES - 1) / RAYCAST_LANES);
+
+__global__ void __launch_bounds__(256) k_raycast_surface(const RaycastArgs r)
+{
+#pragma clang fp contract(off)
+    enum { MARCH, REFINE, DONE };
+    enum { MISS, HIT, UNDER };
+    const QueryArgs& a = r.q;
+    const int sub = (int)(threadIdx.x % RAYCAST_LANES);
+    const unsigned gshift = threadIdx.x & (64u - RAYCAST_LANES);       // the group's first bit in the wave's ballot
+    const size_t ray = (size_t)blockIdx.x * (blockDim.x / RAYCAST_LANES) + threadIdx.x / RAYCAST_LANES;
+    float amp[OCEAN_MAX_CASCADES];
+    query_amplitudes(a, amp);
+    float hsum = 0.0f;
+#pragma unroll
+    for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) hsum = hsum + amp[c];
+    const float hmax = 1.001f * hsum;
+
+    int state = DONE, status = MISS;
+    float ox = 0.0f, oy = 0.0f, oz = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f, t0 = 0.0f, t1 = 0.0f;
+    if (ray < r.count) {
+        const float* o = r.rays + ray * 6;
+        ox = o[0]; oy = o[1]; oz = o[2];
+        dx = o[3]; dy = o[4]; dz = o[5];
+        const float len = sqrtf((dx * dx + dy * dy) + dz * dz);
+        if (len > 0.0f && len <= 3.402823466e+38f) {                   // zero, inf and NaN lengths miss
+            dx = dx / len; dy = dy / len; dz = dz / len;
+            bool empty;
+            if (oy <= -hmax) {
+                status = UNDER;
+                empty = true;
+            } else if (dy < 0.0f) {
+                t0 = fmaxf(0.0f, (hmax - oy) / dy);
+                t1 = fminf(r.max_distance, (-hmax - oy) / dy);
+                empty = t1 < t0;
+            } else if (dy > 0.0f) {
+                t0 = fmaxf(0.0f, (-hmax - oy) / dy);
+                t1 = fminf(r.max_distance, (hmax - oy) / dy);
+                empty = t1 < t0;
+            } else {
+                t0 = 0.0f;
+                t1 = r.max_distance;
+                empty = !(oy < hmax);
+            }
+            if (!empty) state = MARCH;
+        }
+    }
+    const float h = (t1 - t0) / (float)r.steps;
+    int base = 0, round = 0, jb = 0;               // MARCH: index of the group's first sample; REFINE: rounds done, first j of this step
+    float ta = 0.0f, fa = 0.0f, tb = 0.0f, fb = 0.0f, ra = 0.0f, w = 0.0f, thit = 0.0f;   // ra, w: a and (b - a) / 16 of this round
+
+    while (__ballot(state != DONE) != 0ull) {
+        bool valid = false;
+        float x = 0.0f, f = 0.0f;
+        if (state == MARCH) {
+            const int i = base + sub;
+            valid = i <= r.steps;
+            x = i == r.steps ? t1 : t0 + (float)i * h;
+        } else if (state == REFINE) {
+            const int j = jb + sub;
+            valid = j >= 1 && j <= 15;
+            x = ra + (float)j * w;
+        }
+        if (valid) f = (oy + x * dy) - surface_height(a, amp, ox + x * dx, oz + x * dz);
+        const unsigned bits = (unsigned)(__ballot(valid && f <= 0.0f) >> gshift) & ((1u << RAYCAST_LANES) - 1u);
+        const int j = bits ? __builtin_ctz(bits) : RAYCAST_LANES - 1;      // the first sample at or under the water, else the last
+        const int jp = j > 0 ? j - 1 : 0;
+        const float xj = __shfl(x, j, RAYCAST_LANES), fj = __shfl(f, j, RAYCAST_LANES);
+        const float xp = __shfl(x, jp, RAYCAST_LANES), fp = __shfl(f, jp, RAYCAST_LANES);
+        bool bracketed = false;
+        if (state == MARCH) {
+            if (bits && base + j == 0) {                                   // the very first sample is wet
+                status = t0 == 0.0f ? UNDER : HIT;
+                thit = t0;
+                state = DONE;
+            } else if (bits) {
+                if (j > 0) { ta = xp; fa = fp; }                           // else (ta, fa) = the previous step's last sample
+                tb = xj; fb = fj;
+                bracketed = true;
+            } else {
+                ta = xj; fa = fj;                                          // carried into the next step
+                base += RAYCAST_LANES;
+                if (base > r.steps) state = DONE;                          // no sample at or under the water: a miss
+            }
+        } else if (state == REFINE) {
+            if (bits) {
+                if (j > 0 && jb + j >= 2) { ta = xp; fa = fp; }            // else a = s_0 stays, or the previous step's last sample
+                tb = xj; fb = fj;
+                ++round;
+                bracketed = true;
+            } else {
+                ta = xj; fa = fj;                                          // the last sample so far (s_15 at the end of the round)
+                jb += RAYCAST_LANES;
+                if (jb > 15) { ++round; bracketed = true; }                // none of s_1 .. s_15 is wet: [s_15, b]
+            }
+        }
+        if (bracketed) {
+            if (round < r.refine) {
+                state = REFINE;
+                ra = ta;
+                w = (tb - ta) / 16.0f;
+                jb = RAYCAST_J0;
+            } else {
+                status = HIT;
+                thit = ta + (tb - ta) * (fa / (fa - fb));
+                state = DONE;
+            }
+        }
+    }
+
+    if (sub != 0 || ray >= r.count) return;
+    if (status == MISS) {
+        r.out_hit[ray] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        r.out_nrm[ray] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const bool under = status == UNDER;
+    const float qx = under ? ox : ox + thit * dx, qz = under ? oz : oz + thit * dz;
+    const float py = under ? oy : oy + thit * dy;
+    float4 pos, nrm;
+    query_point(a, amp, qx, qz, pos, nrm);
+    r.out_hit[ray] = make_float4(pos.x, pos.y, pos.z, under ? -2.0f : thit);
+    r.out_nrm[ray] = make_float4(nrm.x, nrm.y, nrm.z, py - pos.y);
 }
 
 

@@ -187,6 +187,8 @@ struct ocean_ctx {
     std::vector<float> set_length[MAXD];    //   (recorded when it is enqueued: what ocean_query_surface's Newton step needs)
     float* query_buf = nullptr;     // ocean_query_surface: staging of the points and results, 10 floats per point (grows on demand)
     uint32_t query_capacity = 0;    // points it holds
+    float* ray_buf = nullptr;       // ocean_raycast_surface: staging of the rays and results, 14 floats per ray (grows on demand)
+    uint32_t ray_capacity = 0;      // rays it holds
     unsigned long long* stamps = nullptr;   // diagnostic builds only
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
