@@ -92,7 +92,7 @@ enum {
                                             at once, start spread over a few microseconds so that the early ones store while
                                             the late ones still load -- the three launches of a frame of one 2048^2 tile
                                             (serial and pipelined frames with ramps of their own), nowhere else          */
-    OCEAN_LAUNCH_SPLIT_ORDER     = 512,  /* developer builds only (never set by the shipped library): the frame ran in the split order of
+    OCEAN_LAUNCH_SPLIT_ORDER     = 512,  /* reserved, never set: round 5's developer builds marked frames run in the split order of
                                             profiles/r05_4096_experiments.txt -- z pass and k_xpass_b twice, each time half their work        */
     OCEAN_LAUNCH_WT_INTER        = 2048, /* z pass: fp32 intermediates stored write-through (`sc1`: they leave the XCD's L2 as they are written, no
                                             end-of-kernel write-back burst) -- serial frames at 1024^2 (batches) and 2048^2, single-transform form */

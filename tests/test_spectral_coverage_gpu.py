@@ -181,7 +181,8 @@ def impulse_xi(n):
     """|h0| = AMP on every bin, with the phase that makes the bin's real wave 2 Re(h0 exp(i w T)) = 2 AMP at the checked time: a lone
     bin whose wave happened to be near a zero crossing would leave only the rounding of that cancellation to compare."""
     u = S.unit(n)
-    om = S.make_oracle(n, np.ones((n, n, 2), np.float32)).omega.astype(np.float32)
+    o = S.make_oracle(n, np.ones((n, n, 2), np.float32))      # (held until its array is copied: omega is a view of the oracle's own memory)
+    om = o.omega.astype(np.float32)
     wt = (om * np.float32(T)).astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
         s = np.where(u >= S.AMP * S.CAP, S.AMP / u, 0.0)

@@ -53,7 +53,7 @@ HEADERS = {"ocean.h": SYMBOLS_BOUNDARY, "ocean_consumers.h": SYMBOLS_CONSUMERS, 
 OCEAN_LAUNCH_NT_MAPS, OCEAN_LAUNCH_NT_INTER, OCEAN_LAUNCH_HALF_INTER, OCEAN_LAUNCH_JACOBIAN = 1, 2, 4, 8
 OCEAN_LAUNCH_FP16_SPECTRUM, OCEAN_LAUNCH_FP32_DISPERSION, OCEAN_LAUNCH_SPLIT_LAST_ROUND, OCEAN_LAUNCH_SINGLE_TRANSFORM = 16, 32, 64, 128
 OCEAN_LAUNCH_STAGGERED_START = 256
-OCEAN_LAUNCH_SPLIT_ORDER = 512      # developer builds only
+OCEAN_LAUNCH_SPLIT_ORDER = 512      # reserved, never set (round 5's split frame order)
 OCEAN_LAUNCH_MERGED_X = 1024
 OCEAN_LAUNCH_WT_INTER = 2048
 OCEAN_LAUNCH_ONE_LAUNCH = 4096

@@ -26,19 +26,6 @@ namespace ocean {
 
 using c32 = float2;
 
-// diagnostic builds only (-DOCEAN_STAMPS): per-workgroup clock stamps
-#ifdef OCEAN_STAMPS
-static __device__ unsigned long long* g_stamps = nullptr;
-__device__ __forceinline__ void stamp(int k)
-{
-    if (threadIdx.x == 0 && g_stamps)
-        g_stamps[(size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 32 + k] = clock64();
-}
-#define OCEAN_STAMP(k) ::ocean::stamp(k)
-#else
-#define OCEAN_STAMP(k) do {} while (0)
-#endif
-
 __device__ __forceinline__ c32 cmul(c32 a, c32 b)
 {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -61,16 +48,9 @@ __device__ __forceinline__ c32 toc(v2 a) { return make_float2(a.x, a.y); }
 __device__ __forceinline__ v2 pk_cmul(v2 a, v2 w)           // a * w
 {
     v2 d;
-#ifdef OCEAN_CMUL_SPLIT      // developer A/B: the two-statement form of rounds 2-5
-    v2 t;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(t) : "v"(a), "v"(w));          // (a.x w.x, a.x w.y)
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"                 // (t.x - a.y w.y, t.y + a.y w.x)
-        : "=v"(d) : "v"(a), "v"(w), "v"(t));
-#else
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]\n\t"                                   // (a.x w.x, a.x w.y)
         "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"                 // (t.x - a.y w.y, t.y + a.y w.x)
         : "=&v"(d) : "v"(a), "v"(w));
-#endif
     return d;
 }
 __device__ __forceinline__ v2 pk_add_i(v2 b, v2 a)          // b + i a = (b.x - a.y, b.y + a.x)
@@ -364,7 +344,6 @@ __device__ __forceinline__ void fft_stage(c32* lds, const TW& twr, int tid, In& 
     // NSR: the NS of the stage that wrote the image this stage reads (lds_index_x: per-exchange layouts of single-column batches)
     // WRM: this stage's outputs feed the last stage of a batch whose last exchange is row-major (lds_row_major_last)
     constexpr bool RRM = LAST && !FIRST && lds_row_major_last<N, C, LM, R>();      // ... and the last stage reads that image
-    [[maybe_unused]] constexpr int STAMP_BASE = STAGE;
     constexpr int ITEMS = (N / R) * C;
     constexpr int IT = (ITEMS + T - 1) / T;
     constexpr bool GUARD = (ITEMS % T) != 0;
@@ -390,18 +369,14 @@ __device__ __forceinline__ void fft_stage(c32* lds, const TW& twr, int tid, In& 
                     else if constexpr (RRM) x[i] = ldsv[rb + i * (N / R)];
                     else x[i] = ldsv[rb + lds_delta_x<C, NSR, N>(i * (N / R))];
                 }
-#ifndef OCEAN_ABL_NOFFT
                 if constexpr (NS > 1) apply_twiddles<R>(x, tov(twr.w[STAGE][u]));
                 Dft<R>::run(x);
-#endif
                 const int k = j % NS;
                 const int j0 = (j - k) * R + k;
 #pragma unroll
                 for (int i = 0; i < R; ++i) out(j0 + i * NS, c, toc(x[i]), u, i);
             }
         }
-        OCEAN_STAMP(8 + 3 * STAMP_BASE);
-        OCEAN_STAMP(9 + 3 * STAMP_BASE);
         return;
     }
     v2 x[IT][R];
@@ -416,15 +391,11 @@ __device__ __forceinline__ void fft_stage(c32* lds, const TW& twr, int tid, In& 
                 if constexpr (FIRST) x[u][i] = tov(in(j + i * (N / R), c, u, i));
                 else x[u][i] = ldsv[rb + lds_delta_x<C, NSR, N>(i * (N / R))];
             }
-#ifndef OCEAN_ABL_NOFFT
             if constexpr (NS > 1) apply_twiddles<R>(x[u], tov(twr.w[STAGE][u]));
             Dft<R>::run(x[u]);
-#endif
         }
     }
-    OCEAN_STAMP(8 + 3 * STAMP_BASE);
     __syncthreads();   // every reader of the old image is done
-    OCEAN_STAMP(9 + 3 * STAMP_BASE);
 #pragma unroll
     for (int u = 0; u < IT; ++u) {
         const int w = tid + u * T;
@@ -447,7 +418,6 @@ __device__ __forceinline__ void run_stages(c32* lds, const TW& twr, int tid, In&
     constexpr bool FIRST = STAGE == 0, LAST = STAGE == P::S - 1;
     constexpr bool WRM = STAGE == P::S - 2 && lds_row_major_last<N, C, LM, P::last>();
     fft_stage<N, R, NS, C, T, FIRST, LAST, STAGE, LM, WRM, NSR>(lds, twr, tid, in, out);
-    OCEAN_STAMP(10 + 3 * STAGE);
     if constexpr (!LAST) {
         __syncthreads();
         run_stages<N, C, T, P, STAGE + 1, NS * R, LM>(lds, twr, tid, in, out);

@@ -617,10 +617,10 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     a.mode = c->mode;
     a.start_ramp = 0;       // (set per launch by the launcher where a staggered start pays: ocean_launch.h)
     a.disp_host = c->host_out[0]; a.nrm_host = c->host_out[1];      // (ocean_compute_waves_read, small maps; null otherwise)
-    a.zmask = 15; a.xb_roles = 3;                   // (per launch: the launcher's frame order)
+    a.zmask = 15; a.xb_roles = 3;                   // (every transform in the one z pass; the x-axis roles per launch: ocean_launch.h)
     a.xcd_rot = 0;
 #ifdef OCEAN_DEVELOPER
-    if (const char* xr = getenv("OCEAN_XCD_ROT")) a.xcd_rot = atoi(xr) % 7;      // (read per frame: tools/xcd_rot.py flips it between windows)
+    if (const char* xr = getenv("OCEAN_XCD_ROT")) a.xcd_rot = atoi(xr) % 7;      // (read per frame: tools/slow_window.py flips it between windows)
 #endif
     a.rec_mode = track ? 2 : 1;                     // what the frame's LAST launch does with the completion records
     // maps beyond the memory-side cache, or several frames in flight: stream the maps past it
@@ -1709,7 +1709,7 @@ int ocean_time_frames(ocean_t* c, float t0, float dt, int warmup, int frames, fl
             for (int l = 0; l < c->launch_count; ++l) {
                 float m = 0.f;
                 HIP_TRY(hipEventElapsedTime(&m, c->mark_ev[set][2 * l], c->mark_ev[set][2 * l + 1]));
-                acc[c->launch_kernel[l]] += m;      // a kernel that runs twice per frame (split order) reports the sum
+                acc[c->launch_kernel[l]] += m;
             }
             ++counted;
             return OCEAN_OK;
@@ -1739,21 +1739,6 @@ int ocean_time_frames(ocean_t* c, float t0, float dt, int warmup, int frames, fl
     return OCEAN_OK;
 }
 
-#ifdef OCEAN_XB_TRACE
-// diagnostic build only (tools/archive/xb_trace.py): enable = allocate the trace buffer (the next frames' k_xpass_b fill it); host_out = copy it out
-extern "C" int ocean_debug_xb_trace(ocean_t* c, int enable, unsigned long long* host_out, size_t count)
-{
-    if (!c) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
-    if (enable && !c->stamps) {
-        HIP_TRY(hipMalloc(&c->stamps, (size_t)1 << 20));
-        HIP_TRY(hipMemset(c->stamps, 0, (size_t)1 << 20));
-    }
-    if (host_out) HIP_TRY(hipMemcpy(host_out, c->stamps, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return OCEAN_OK;
-}
-#endif
 #ifdef OCEAN_CLOCKPROBE
 // diagnostic build only (tools/slow_window.py): enable = allocate the probe buffer (the next single-transform z passes fill it, record
 // [frame_seq % 4096][workgroup][4]); host_out = copy `count` 64-bit words out, starting at word `first`
@@ -1771,21 +1756,6 @@ extern "C" int ocean_debug_clockprobe(ocean_t* c, int enable, unsigned long long
         if (!c->stamps || (first + count) * sizeof(unsigned long long) > bytes) return OCEAN_E_INVALID;
         HIP_TRY(hipMemcpy(host_out, c->stamps + first, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
-    return OCEAN_OK;
-}
-#endif
-#ifdef OCEAN_STAMPS
-// diagnostic build only: per-workgroup clock stamps of the last frame
-int ocean_debug_stamps(ocean_t* c, int enable, unsigned long long* host_out, size_t count)
-{
-    if (!c) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
-    if (enable && !c->stamps) {
-        HIP_TRY(hipMalloc(&c->stamps, (size_t)1 << 24));
-        HIP_TRY(hipMemset(c->stamps, 0, (size_t)1 << 24));
-    }
-    if (host_out) HIP_TRY(hipMemcpy(host_out, c->stamps, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return OCEAN_OK;
 }
 #endif

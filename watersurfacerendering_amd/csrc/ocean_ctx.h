@@ -13,7 +13,7 @@
 #include "ocean_kernels.h"
 
 constexpr int MAXD = 8;     // maximum pipeline depth (independent frame chains)
-constexpr int OCEAN_MAX_LAUNCHES = 5;   // launches per frame: three (five in the developer-only split order: ocean_launch.h)
+constexpr int OCEAN_MAX_LAUNCHES = 3;   // launches per frame: at most three (ocean_launch.h)
 
 // ---- launch and store-policy heuristics: every measured constant in ONE place -----------------------------------------
 // The rules are written in quantities of the device and of the launch -- compute units x resident workgroups per unit (asked of the runtime:
@@ -193,8 +193,8 @@ struct ocean_ctx {
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
     hipEvent_t mark_ev[MAXD][2 * OCEAN_MAX_LAUNCHES] = {};   // per-launch timing: (start, stop) of each launch of a frame
-    int launch_count = 3;               // launches of the most recent frame (3; 5 in the developer-only split order) and the kernel (0 z pass, 1 k_xpass_b,
-    int launch_kernel[OCEAN_MAX_LAUNCHES] = {0, 1, 2, 0, 1};   //   2 k_xpass_disp) each of them ran: ocean_time_frames sums a kernel's launches
+    int launch_count = 3;               // launches of the most recent frame (3; 2 with the merged x pass, 1 in a one-launch frame) and the kernel (0 z pass, 1 k_xpass_b,
+    int launch_kernel[OCEAN_MAX_LAUNCHES] = {0, 1, 2};   //   2 k_xpass_disp) each of them ran: ocean_time_frames adds them up per kernel
     ocean_launch_info last_launch[3] = {};  // what the most recent frame launched (ocean_last_launch)
     hipEvent_t z_done[MAXD] = {};       // pipelined frames right after a drain: recorded behind a chain's z pass (see enqueue_frame)
     hipEvent_t after_z = nullptr;       // what launch_frame records behind the z pass of the frame being enqueued (null: nothing)

@@ -40,11 +40,9 @@
 #include <type_traits>
 #include "fft_engine.h"
 
-// Diagnostic builds (never shipped; `make -C csrc variant NAME=x DEFS=...`): -DOCEAN_STAMPS records
-// per-workgroup phase clocks (tools/archive/stamps.py); -DOCEAN_ABL_NOLOAD / _NOSTORE / _NOMAPSTORE / _NOFFT /
-// _NOIN / _SINCOS remove the global loads, the intermediate stores, the map stores, the butterfly
-// arithmetic, the z-pass input arithmetic or the sincos -- results are then wrong on purpose; they
-// only attribute time.
+// (The per-workgroup phase clocks and the ablation builds that attributed time in rounds 1-6 -- global loads, intermediate stores,
+// map stores, butterfly arithmetic, z-pass input arithmetic or sincos removed, results wrong on purpose -- are no longer
+// carried: the logs under profiles/ have their figures, e.g. r03_xpass_trace.txt and r04_zpass_experiments.txt item 7.)
 namespace ocean {
 
 typedef float ocean_f4 __attribute__((ext_vector_type(4)));
@@ -62,13 +60,8 @@ __device__ __forceinline__ void store_nt(float4* p, float4 v)
 // picks per launch.  The texel index is turned into a 32-bit byte offset (N <= 4096: < 2^28)
 // so the store addresses as scalar base + vector offset.
 // Write-through (`sc1`) stores: the line leaves the XCD's L2 as it is written.  Adopted for the fp32 intermediates up to 2048 (store_z, WT);
-// measured and rejected for the maps (developer A/B: -DOCEAN_MAP_SC1=1 stores the maps of the plain form that way, =2 those of the
+// measured and rejected for the maps (round 5 A/B: the maps of the plain form stored that way, or those of the
 // non-temporal form as well: k_xpass_disp 16.0 -> 17.6-18.2 us at 2048^2, the pipelined and 4096^2 frames +40 %; profiles/r05_store_policy_experiments.txt).
-__device__ __forceinline__ void store_f4_sc1(float4* base, unsigned byte_off, float4 v)
-{
-    const ocean_f4 t = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc1" ::"v"(byte_off), "v"(t), "s"(base) : "memory");
-}
 __device__ __forceinline__ void store_f2_sc1(float2* base, unsigned byte_off, float2 v)
 {
     typedef float f2v __attribute__((ext_vector_type(2)));
@@ -77,16 +70,9 @@ __device__ __forceinline__ void store_f2_sc1(float2* base, unsigned byte_off, fl
 }
 template <bool NTS> __device__ __forceinline__ void store_map(float4* base, unsigned texel, float4 v)
 {
-#ifdef OCEAN_ABL_NOMAPSTORE      // ablation build: the map texels are computed but never written
-    asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-#else
-#ifdef OCEAN_MAP_SC1
-    if constexpr (!NTS || OCEAN_MAP_SC1 == 2) { store_f4_sc1(base, texel * 16u, v); return; }
-#endif
     float4* p = reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + (texel * 16u));
     if constexpr (NTS) store_nt(p, v);
     else *p = v;
-#endif
 }
 #define OCEAN_STORE(base, texel, val) store_map<NTS>((base), (unsigned)(texel), (val))
 // The same texel to a SECOND destination as well: the caller's page-locked host array, through its device address (ocean_compute_waves_read,
@@ -151,13 +137,7 @@ template <bool Z16> __device__ __forceinline__ float2 load_z(const float2* base,
         const float2 f = __half22float2(h);
         return make_float2(f.x * unscale, f.y * (unscale_y != 0.0f ? unscale_y : unscale));
     } else {
-#ifdef OCEAN_XLOAD_NT      // developer A/B: the x passes read the intermediates, each element once, with non-temporal loads
-        typedef float f2nt __attribute__((ext_vector_type(2)));
-        const f2nt t = __builtin_nontemporal_load(reinterpret_cast<const f2nt*>(reinterpret_cast<const char*>(base) + idx * 8u));
-        return make_float2(t.x, t.y);
-#else
         return *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(base) + idx * 8u);
-#endif
     }
 }
 template <class T> __device__ __forceinline__ T& at32(T* base, unsigned idx)
@@ -223,11 +203,11 @@ struct FrameArgs {
                              // 3 JACOBIAN (FULL7 + the cross derivative; displacement.w = Jacobian of the horizontal displacement)
     // ---- set per launch by ocean_launch.h (ocean_api.hip leaves the defaults) ----
     int zmask;               // z pass: the transforms this launch runs -- bit 0 pair 0, bit 1 pair 1, bit 2 pair 2, bit 3 the height (pair 3 in the
-                             // Jacobian mode).  15 = all (one z pass per frame); the split frame order (launch_frame) runs {height, pair 0} and
-                             // {pair 1, pair 2} as two launches, each animating the spectrum for itself
+                             // Jacobian mode).  The host always passes 15 = all (one z pass per frame); round 5's split frame order ran {height, pair 0} and
+                             // {pair 1, pair 2} as two launches, each animating the spectrum for itself (profiles/r05_4096_experiments.txt)
     int xb_roles;            // k_xpass_b: bit 0 the HEIGHT workgroups, bit 1 the NORMAL workgroups (3 = both in one launch), bit 2 the DISP
                              // workgroups as well (7 = the merged x pass: the whole x axis in one launch, no k_xpass_disp)
-    int xcd_rot;             // developer builds only (OCEAN_XCD_ROT, tools/xcd_rot.py): the single-transform z pass hands the column groups of XCDs 1..7 round
+    int xcd_rot;             // developer builds only (OCEAN_XCD_ROT, tools/slow_window.py): the single-transform z pass hands the column groups of XCDs 1..7 round
                              // by this many places -- which XCD writes which part of the intermediates -- 0 in the shipped library
     float4* disp_host;       // [tiles][N][N] or null: the caller's page-locked destinations of ocean_compute_waves_read (device addresses): the x passes
     float4* nrm_host;        //                        store every map texel there as well (store_map_host)
@@ -322,14 +302,7 @@ __device__ __forceinline__ void spectrum_form(const FrameArgs& a, F&& f)
     else f(std::false_type{}, std::false_type{});
 }
 // tile sizes whose spectrum is read with non-temporal loads (the usual form: fp32 spectrum, 16-bit dispersion)
-#ifndef OCEAN_SPEC_NT_MIN
-#define OCEAN_SPEC_NT_MIN 4096
-#endif
-#ifdef OCEAN_SPEC_NT_ALWAYS
-template <int N, bool ZNT> constexpr bool spectrum_nt() { return N >= OCEAN_SPEC_NT_MIN; }
-#else
-template <int N, bool ZNT> constexpr bool spectrum_nt() { return N >= OCEAN_SPEC_NT_MIN && !ZNT; }
-#endif
+template <int N, bool ZNT> constexpr bool spectrum_nt() { return N >= 4096 && !ZNT; }
 template <int N, bool H16, bool W16, bool ZNT = false>
 __device__ __forceinline__ void zpass_load_pair(const FrameArgs& a, int tile, int col, int n, float h16s, float base,
                                                 float4& ha, float2& hb0, float2& hb1, float2& w)
@@ -338,13 +311,9 @@ __device__ __forceinline__ void zpass_load_pair(const FrameArgs& a, int tile, in
     const int mcol = (N - col) & (N - 1);
     const size_t g = (size_t)col * N + n;
     const size_t m0 = (size_t)mcol * N + ((N - n) & (N - 1)), m1 = (size_t)mcol * N + (N - n - 1);
-#ifdef OCEAN_ABL_NOLOAD
-    ha = make_float4(1.f + g, 2.f, 3.f, 4.f); hb0 = make_float2(0.5f, 1.5f); hb1 = make_float2(2.5f, 3.5f); w = make_float2(0.5f, 0.25f);
-    return;
-#endif
     if constexpr (spectrum_nt<N, ZNT>() && !H16 && W16) {
         // beyond the memory-side cache (4096^2: 151 MB of spectrum, read once per z pass): streamed past it, so that the intermediates
-        // -- written here, re-read by the x pass right behind -- are what stays resident (ocean_launch.h: the split frame order)
+        // -- written here, re-read by the x pass right behind -- are what stays resident (profiles/r05_4096_experiments.txt)
         typedef float nt4 __attribute__((ext_vector_type(4)));
         typedef float nt2 __attribute__((ext_vector_type(2)));
         const float2* __restrict__ h0 = a.h0 + tile * n2;
@@ -379,22 +348,12 @@ __device__ __forceinline__ void animate_with_mirror(float2 h0a, float2 h0b, floa
 {
     const float wt = mul_nocontract(w, t);      // ONE fp32 multiply, like the reference (.h:267)
     float s, c;
-#ifdef OCEAN_ABL_SINCOS
-    s = wt * 1e-4f; c = 1.0f - s;
-#else
     sincos_f32(wt, s, c);
-#endif
     av = height_re(h0a.x, h0a.y, c, s);
     bv = height_re(h0b.x, h0b.y, c, s);
 }
 
 // ---- half-spectrum storage geometry -------------------------------------------
-#ifndef OCEAN_ZTILE
-#define OCEAN_ZTILE 8          // rows per block of the intermediates (fp32: 64-byte pieces)
-#endif
-#ifndef OCEAN_ZTILE_H
-#define OCEAN_ZTILE_H 16       // the same for half2 intermediates (64-byte pieces again)
-#endif
 template <int N> struct Half {
     static constexpr int NU = N / 2 + 1;          // columns (units) / rows kept: 0..N/2
     static constexpr int NUP = (N / 2 + 16) & ~15;   // rows 0..N/2 padded to a multiple of 16
@@ -405,21 +364,19 @@ template <int N> struct Half {
     // element (column nb, side, row q) of a packed pair's group, and (column nb, row q) of the height's half plane:
     // row-blocked, [q / ZB][side][nb][q % ZB], so that an x-pass workgroup -- which owns a few rows q and walks all columns
     // nb -- reads one dense run per side instead of a small piece out of every column's 16.5 KB run, while the z pass still
-    // writes ZB units = 64 bytes at a time (OCEAN_ZTILE = 0: the column-major layout [nb][side][q] of round 1;
-    // profiles/r02_layout_experiments.txt has the A/B of 4-, 8- and 16-row blocks).
-    template <bool Z16> static constexpr int zb() { return OCEAN_ZTILE ? (Z16 ? OCEAN_ZTILE_H : OCEAN_ZTILE) : 8; }
+    // writes ZB units = 64 bytes at a time: 8 rows per block in fp32, 16 in the half2 form (round 1 had the column-major
+    // layout [nb][side][q]; profiles/r02_layout_experiments.txt has the A/B of 4-, 8- and 16-row blocks).
+    template <bool Z16> static constexpr int zb() { return Z16 ? 16 : 8; }
     static_assert(NUP % 16 == 0, "row blocks");
     template <bool Z16> static __device__ __forceinline__ unsigned zidx(int nb, int side, int q)
     {
         constexpr int ZB = zb<Z16>();
-        if constexpr (OCEAN_ZTILE != 0) return (unsigned)(((q / ZB) * 2 + side) * (NU * ZB) + nb * ZB + (q % ZB));
-        else return (unsigned)((nb * 2 + side) * NUP + q);
+        return (unsigned)(((q / ZB) * 2 + side) * (NU * ZB) + nb * ZB + (q % ZB));
     }
     template <bool Z16> static __device__ __forceinline__ unsigned zhidx(int nb, int q)
     {
         constexpr int ZB = zb<Z16>() > 8 ? zb<Z16>() : 8;       // the height role reads eight units per column
-        if constexpr (OCEAN_ZTILE != 0) return (unsigned)((q / ZB) * (NU * ZB) + nb * ZB + (q % ZB));
-        else return (unsigned)(nb * NUP + q);
+        return (unsigned)((q / ZB) * (NU * ZB) + nb * ZB + (q % ZB));
     }
 };
 // raw height of map row u at column p: rows of N floats, so that a wave working on one row reads
@@ -447,7 +404,7 @@ template <int N, int T, class P, int ZC, bool Z16> struct ZStore {
     static constexpr int ZB = HF::template zb<Z16>(), ZBH = ZB > 8 ? ZB : 8;
     // (not for the half2 four-transform form -- 256^2 and 512^2 with ocean_set_intermediate_precision(16): there the compiler
     //  leaves the kernel's argument block and a closure in scratch memory with this path, 344 bytes of stack)
-    static constexpr bool FAST = OCEAN_ZTILE != 0 && S >= ZBH && S % ZBH == 0 && (N / 2) % S == 0 && !(Z16 && ZC == 4);
+    static constexpr bool FAST = S >= ZBH && S % ZBH == 0 && (N / 2) % S == 0 && !(Z16 && ZC == 4);
     int b0[LS::IT], b1[LS::IT], bh[LS::IT];
     // A base is read through an empty asm: otherwise a choice between two outputs' positions (c ? height : pair 2, ...) is folded
     // into ONE load with a selected address, which pins the three small arrays in scratch memory instead of registers.
@@ -497,13 +454,7 @@ template <int N, int T, class P, int ZC, bool Z16> struct ZStore {
     }
 };
 
-// (Round 5's half-size real-input transform of the height -- built, measured, not adopted -- lives in experimental/zpass_half_height.h and is
-//  compiled only into developer builds that define OCEAN_HALF_HEIGHT_MIN.)
-#ifdef OCEAN_HALF_HEIGHT_MIN
-#include "experimental/zpass_half_height.h"
-#else
-template <int N> constexpr bool zpass_half_height() { return false; }
-#endif
+// (Round 5's half-size real-input transform of the height was built, measured and not adopted: profiles/r05_zpass_experiments.txt.)
 
 // The four z-axis transforms of one spectrum column (see k_zpass).  COL0 = Nyquist
 // column nb == 0, the only one where Tx = S- along the whole column.
@@ -514,10 +465,7 @@ template <int N> constexpr bool zpass_half_height() { return false; }
 // At 1024^2 it is slower (14.9 -> 16.5 us) and from 2048 up the two-batch form keeps three
 // workgroups per CU.  (The same idea for the normal-map role -- pairs 1 and 2 as one batch of 2 C columns -- was
 // measured 50-60 % slower at both sizes; profiles/r02_small_tile_experiments.txt.)
-#ifndef OCEAN_ZC4
-#define OCEAN_ZC4 1
-#endif
-template <int N> constexpr int zpass_columns() { return (OCEAN_ZC4 && (N == 512 || N == 256)) ? 4 : 2; }
+template <int N> constexpr int zpass_columns() { return (N == 512 || N == 256) ? 4 : 2; }
 // Spectrum columns per z-pass workgroup.  Two NEIGHBOURING columns (each batch = the same pair of both columns) make every
 // store instruction of the last stage cover whole 128-byte lines of the row-blocked intermediates (2 x 64-byte pieces side by
 // side) instead of half lines -- what the non-temporal stores of big tiles and batches need.  Costs N more floats of LDS (a
@@ -609,7 +557,6 @@ __device__ __forceinline__ void zpass_transforms(const FrameArgs& a, c32* fbuf, 
             store_z<ZNT, Z16, ZWT>(zt, (unsigned)c * (unsigned)HF::Z_GROUP + pos, v, c == 0 ? su : sk);
         };
         batch_fft<N, 4, T, P>(fbuf, twr, tid, in, out);
-        OCEAN_STAMP(3);
         return;
     } else {
     // -- batch A: slot 0 = pair 0 (Dx, Dz), slot 1 = pair 1 (sx, sz) ------------
@@ -618,9 +565,6 @@ __device__ __forceinline__ void zpass_transforms(const FrameArgs& a, c32* fbuf, 
 #pragma clang fp contract(off)
             float sv, tx, tz;
             fetch(e, sv, tx, tz);
-#ifdef OCEAN_ABL_NOIN
-            return make_float2(sv, tx);
-#endif
             // (same operations, same order as zpass_input<0/1>, no contraction: bit-identical to the two-column variant)
             const float kz = kzt[e];
             const float d = __builtin_fmaf(kz, kz, kx2);
@@ -629,13 +573,9 @@ __device__ __forceinline__ void zpass_transforms(const FrameArgs& a, c32* fbuf, 
             return make_float2(kz * f * tz, -kx * f * tx);
         };
         auto out = [&](int p, int c, c32 v, int u, int i) {
-#ifdef OCEAN_ABL_NOSTORE
-            asm volatile("" ::"v"(v.x), "v"(v.y)); if (p >= 0) return;
-#endif
             store_z<ZNT, Z16, ZWT>(zt, (unsigned)c * (unsigned)HF::Z_GROUP + zo.pos(nb, p, u, i), v, c ? sk : su);
         };
         batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
-        OCEAN_STAMP(2);
     }
     // -- batch B: slot 0 = pair 2 (dDx/dx, dDz/dz), slot 1 = height ----------------
     // OCEAN_MODE_JACOBIAN: slot 1 becomes pair 3 = (height, dDx/dz): the cross derivative's spectrum
@@ -649,9 +589,6 @@ __device__ __forceinline__ void zpass_transforms(const FrameArgs& a, c32* fbuf, 
 #pragma clang fp contract(off)
             float sv, tx, tz;
             fetch(e, sv, tx, tz);
-#ifdef OCEAN_ABL_NOIN
-            return make_float2(sv, tx);
-#endif
             const float kz = kzt[e];
             // cross derivative: kx kz / |k| is odd in kx and in kz separately, so on the self-mirrored Nyquist column
             // (nb == 0) or row (e == 0) -- where one component of k(-idx) keeps its sign -- its Hermitian part takes
@@ -665,36 +602,14 @@ __device__ __forceinline__ void zpass_transforms(const FrameArgs& a, c32* fbuf, 
             return make_float2(c ? sv : kx2 * g, c ? (jac ? g3 * (kx * kz * inv * tc) : 0.0f) : kz2 * g);
         };
         auto out = [&](int p, int c, c32 v, int u, int i) {
-#ifdef OCEAN_ABL_NOSTORE
-            asm volatile("" ::"v"(v.x), "v"(v.y)); if (p >= 0) return;
-#endif
             if (c) {
                 if (jac) store_z<ZNT, Z16, ZWT>(z3, zo.pos(nb, p, u, i), v, s3);
-                else if constexpr (zpass_half_height<N>()) return;                               // (the height follows below, as the other forms compute it)
                 else if (zo.keeps(p, i)) store_z<ZNT, Z16, ZWT>(zh, zo.hpos(nb, p, u, i), v, su);     // real input: other half is the conjugate
                 return;
             }
             store_z<ZNT, Z16, ZWT>(zt, 2u * (unsigned)HF::Z_GROUP + zo.pos(nb, p, u, i), v, sk);
         };
         batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
-        OCEAN_STAMP(3);
-#ifdef OCEAN_HALF_HEIGHT_MIN
-        if constexpr (zpass_half_height<N>()) {
-            // from 2048 points up every form of the z pass computes the height as a real-input transform (zpass_height_half), so that a
-            // column's bits do not depend on the form that happened to run it (here: the lone columns 0, 1 and N/2 of the two-column kernel)
-            if (!jac) {
-                __syncthreads();                    // the batch's last stage has read the image
-                using HT = HalfHeightTwiddles<N, T, 1>;
-                typename HT::type twh;
-                c32 wk[HT::ITW];
-                HT::from_table(a.tw, tid, twh, wk);
-                float* const spx[1] = {const_cast<float*>(sp)};
-                const int cols[1] = {nb};
-                zpass_height_half<N, T, 1, ZNT, Z16>(a, fbuf, spx, twh, wk, tid, zh, cols, su,
-                                                      [&](int e, int) { asm("" : "+v"(e)); float sv, tx, tz; fetch(e, sv, tx, tz); return sv; });
-            }
-        }
-#endif
     }
     }
 }
@@ -798,20 +713,6 @@ __device__ __forceinline__ void zpass_two_columns(const FrameArgs& a, unsigned c
         auto out = [&](int p, int c, c32 v, int u, int i) { store_z<ZNT, Z16>(zt, 2u * (unsigned)HF::Z_GROUP + zo.pos(nb0 + c, p, u, i), v, sk); };
         batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
     }
-#ifdef OCEAN_HALF_HEIGHT_MIN
-    if constexpr (zpass_half_height<N>()) {
-        if ((a.zmask & 8) && !jac) {      // both columns' heights as real-input transforms (zpass_height_half: the single-transform form's bits)
-            using HT = HalfHeightTwiddles<N, T, 2>;
-            typename HT::type twh;
-            c32 wk[HT::ITW];
-            HT::from_full(twr, twh, wk);
-            float* const spx[2] = {sp0, sp1};
-            const int cols[2] = {nb0, nb0 + 1};
-            zpass_height_half<N, T, 2, ZNT, Z16>(a, fbuf, spx, twh, wk, tid, zh, cols, su, [&](int e, int c) { return c ? sp1[e] : sp0[e]; });
-            return;
-        }
-    }
-#endif
     if (a.zmask & 8) {   // height (or pair 3 = (height, cross derivative) of the Jacobian mode)
         auto in = [&](int e, int c, int, int i) -> c32 {
             float sv, tz, kx, kx2; fetch(e, c, sv, tz, kx, kx2);
@@ -844,9 +745,6 @@ __device__ __forceinline__ void zpass_two_columns(const FrameArgs& a, unsigned c
 // needs 62 VGPRs and would fit four, but its 51 KB of LDS allow three); 1024 and 4096 keep the looser bound
 template <int N> constexpr int zpass_min_waves() { return N == 2048 ? 6 : (N >= 1024 ? 3 : 1); }
 // (two columns per workgroup: since round 4 its kz live in registers, the LDS footprint is the one-column form's and so is the bound)
-#ifndef OCEAN_ZLB
-#define OCEAN_ZLB zpass_min_waves<N>()
-#endif
 // The body of k_zpass as a device function: k_frame (the one-launch frame of pipelined small tiles) runs it for its first N/2 + 1 workgroups.
 // bx / gx: the workgroup's index and count among the z-pass workgroups of its tile; ONE: part of a one-launch frame -- the intermediates go out
 // write-through and the per-tile words the x-axis workgroups of the SAME launch update by atomics are reset write-through too.
@@ -874,7 +772,6 @@ __device__ __forceinline__ void zpass_body(const FrameArgs& a, unsigned char* sm
     const float h16s = a.h0h ? a.h0_inv_scale[tile] : 1.0f;
     const float base = a.omega_q ? a.base_freq[tile] : 0.0f;
 
-    OCEAN_STAMP(0);
     // -- phase 1: animate column nb with its mirror nbb (zpass_load_pair); all loads issued before the first sincos.
     // S- is needed along the whole column only for the Nyquist column nb == 0 (Tx = S-); every other column needs just
     // S-(0) (Tz at e == 0) and keeps the kz table in LDS instead.  The Nyquist column pairs with itself (nbb == 0): S+ is
@@ -923,7 +820,6 @@ __device__ __forceinline__ void zpass_body(const FrameArgs& a, unsigned char* sm
     }
     __syncthreads();
     const float sm0 = raw[0];
-    OCEAN_STAMP(1);
 
     if (col0) zpass_transforms<N, T, P, true, ZNT, Z16, ZC, ONE>(a, fbuf, sp, kzt, twr, k1[nb], sm0, tid, tile, nb, batches);
     else zpass_transforms<N, T, P, false, ZNT, Z16, ZC, ONE>(a, fbuf, sp, kzt, twr, k1[nb], sm0, tid, tile, nb, batches);
@@ -943,17 +839,12 @@ __device__ __forceinline__ void zpass_body(const FrameArgs& a, unsigned char* sm
         __syncthreads();            // the slowest wave is done with the FFT image before the next column's h~ overwrites it
         one_column(1, 3);
     } else {
-        int nb = bx;
-        const int batches = 3;
-#if OCEAN_ZTILE
-        nb = xcd_swizzle(nb, gx);     // neighbouring columns write neighbouring pieces of the same lines: same XCD, same L2
-#endif
-        one_column(nb, batches);
+        one_column(xcd_swizzle(bx, gx), 3);     // neighbouring columns write neighbouring pieces of the same lines: same XCD, same L2
     }
 }
 
 template <int N, int T, class P = Plan<N>, bool ZNT = false, bool Z16 = false, int ZW = 1, bool FAST = true>
-__global__ void __launch_bounds__(T, OCEAN_ZLB) k_zpass(const FrameArgs a)
+__global__ void __launch_bounds__(T, zpass_min_waves<N>()) k_zpass(const FrameArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     zpass_body<N, T, P, ZNT, Z16, ZW, FAST>(a, smem, (int)blockIdx.x, (int)gridDim.x);
@@ -1054,7 +945,7 @@ __device__ __forceinline__ void zpass_single_transforms(const FrameArgs& a, c32*
             tc = tz;
         }
     };
-    // (a.zmask: which of the four this launch runs -- all of them, or one half of the split frame order; wave-uniform)
+    // (a.zmask: which of the four this launch runs -- all of them: only round 5's split frame order ran halves; wave-uniform)
     if (a.mode != 2) {
         if (a.zmask & 1) {   // pair 0: (uz Tz, -ux Tx)
             auto in = [&](int e, int, int, int i) -> c32 {
@@ -1081,25 +972,6 @@ __device__ __forceinline__ void zpass_single_transforms(const FrameArgs& a, c32*
         auto out = [&](int p, int, c32 v, int u, int i) { store_z<ZNT, Z16, ZWT>(zt, 2u * (unsigned)HF::Z_GROUP + zo.pos(nb, p, u, i), v, sk); };
         batch_fft<N, 1, T, P>(fbuf, twr, tid, in, out);
     }
-#ifdef OCEAN_HALF_HEIGHT_MIN
-    if constexpr (zpass_half_height<N>()) {
-        if ((a.zmask & 8) && !jac) {      // the height as a real-input transform: half the size + one split step (zpass_height_half)
-            using HT = HalfHeightTwiddles<N, T, 1>;
-            typename HT::type twh;
-            c32 wk[HT::ITW];
-            HT::from_full(twr, twh, wk);
-            float* const spx[1] = {const_cast<float*>(sp)};
-            const int cols[1] = {nb};
-            zpass_height_half<N, T, 1, ZNT, Z16>(a, fbuf, spx, twh, wk, tid, zh, cols, su,
-                                                  [&](int e, int) {
-                                                      // (opaque index: otherwise the Nyquist column's mirror index (N - e) % N is recognised as phase 1's and kept
-                                                      //  alive -- through a spill -- across the whole kernel instead of being recomputed in two instructions)
-                                                      asm("" : "+v"(e));
-                                                      float sv, tx, tz, tc; fetch(e, sv, tx, tz, tc); return sv; });
-            return;
-        }
-    }
-#endif
     if (a.zmask & 8) {   // height (or pair 3 = (height, cross derivative) of the Jacobian mode)
         auto in = [&](int e, int, int, int i) -> c32 {
             float sv, tx, tz, tc; fetch(e, sv, tx, tz, tc);
@@ -1269,9 +1141,6 @@ template <int N, bool Z16 = false>
 __device__ __forceinline__ c32 load_pair_column(const float2* __restrict__ zg, int mf, int u, float eps, float unscale = 1.0f, float unscale_y = 0.0f)
 {
     using HF = Half<N>;
-#ifdef OCEAN_ABL_NOLOAD
-    return make_float2(1.0f + mf, 0.5f * u);
-#endif
     if (mf <= N / 2) return load_z<Z16>(zg, HF::template zidx<Z16>(mf, 0, u), unscale, unscale_y);
     // mirror of the self-mirrored units 0 and N/2 is the unit itself (side 0)
     const int side = (u == 0 || u == N / 2) ? 0 : 1;
@@ -1309,26 +1178,6 @@ __device__ __forceinline__ void for_each_output(int tid, F f)
 // one height launch, then all three pairs per workgroup with register prefetch -- was
 // measured slower at every size and removed.)
 // ============================================================================
-#ifdef OCEAN_XB_TRACE
-// diagnostic build only (tools/archive/xb_trace.py, profiles/r03_xpass_trace.txt): per workgroup of the two x passes, where and when it ran --
-// [record][4] = {start, end (100 MHz wall clock), HW_REG_HW_ID, HW_REG_XCC_ID}; records 0.. = k_xpass_b's workgroups, 512.. = k_xpass_disp's
-static __device__ unsigned long long* g_xb_trace = nullptr;
-struct XbTrace {
-    unsigned long long* p;
-    __device__ explicit XbTrace(unsigned base = 0) : p(nullptr)
-    {
-        if (threadIdx.x == 0 && g_xb_trace && blockIdx.y == 0) {
-            p = g_xb_trace + 4 * (size_t)(base + blockIdx.x);
-            unsigned hwid, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            p[2] = hwid; p[3] = xcc;
-            p[0] = wall_clock64();
-        }
-    }
-    __device__ ~XbTrace() { if (p) p[1] = wall_clock64(); }       // thread 0 leaves the kernel: its last store has been issued (not drained)
-};
-#endif
 // Row groups of the x passes: NB - 1 groups of C map rows and the group of row N/2, which with C - 1 padding rows would run C transforms
 // for one useful row and -- as the (NB)th workgroup on 256 CUs -- close the launch (per-workgroup trace, profiles/r03_xpass_trace.txt:
 // the 257th workgroup of the displacement pass is the only one that shares a CU).  From 1024 up that group runs ONE transform per
@@ -1338,7 +1187,7 @@ template <int N, int C> constexpr bool xpass_single_row_group() { return C > 1 &
 // all-padding group behind them)
 template <int N, int C> constexpr int xpass_height_groups() { return (N / 2 + 1 + 2 * C - 1) / (2 * C); }
 
-// Completion record of a frame.  The workgroup of the frame's last launch (the displacement pass; the normal-map role in the split frame order) that finishes LAST hands, per tile, one 16-byte record
+// Completion record of a frame.  The workgroup of the frame's last launch (the displacement pass) that finishes LAST hands, per tile, one 16-byte record
 // (min key, max key, frame sequence number, 0) to host-coherent memory: a synchronous ComputeWaves returns from a short poll of
 // those words instead of a stream synchronisation (ocean_compute_waves; 13-16 us of wake-up per call at the reference's call
 // shape, WaterSurfaceMesh.cpp:145-154).  A record is one store instruction of one lane -- the host never sees half of one -- and
@@ -1398,9 +1247,6 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     c32* fbuf = reinterpret_cast<c32*>(smem);
     const int tid = threadIdx.x;
     const int tile = blockIdx.y;
-#ifdef OCEAN_XB_TRACE
-    XbTrace xb_trace_;
-#endif
     constexpr int LM = 1;                                 // last-stage lane layout (fft_engine.h): a wave = one map row, 1 KiB bursts
     TwiddleRegs<N, C, T, P, LM> twr;
     twr.load(a.tw, tid);
@@ -1541,8 +1387,8 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     // same box, interleaved) and costs nothing anywhere else.
     // (From 2048 up, where a tile's workgroups outnumber the CUs; at 512^2 and 1024^2 -- every workgroup alone on a CU -- the plain swizzle is
     // 0.3-0.5 us faster and stays.)
-    // (the role's body as a lambda: its reduced modes leave early, and in the split frame order -- where this is the frame's LAST launch --
-    //  every thread of the workgroup must still reach frame_records below)
+    // (the role's body as a lambda: its reduced modes leave early, and every thread of the workgroup must still
+    //  reach frame_records below)
     auto normal_role = [&]() {
     const int nid = bx - HB;
     const int u0 = (N >= 2048 ? (nid == 0 ? NB - 1 : xcd_swizzle(nid - 1, NB - 1)) : xcd_swizzle(nid, NB)) * C;
@@ -1702,7 +1548,7 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     else if (!JAC && merged_launch && bx >= HB + NB) disp_role();
     else normal_role();
     // the launch's records: the early form needs the final height keys -- the first NORMAL workgroup of a launch behind the HEIGHT
-    // workgroups' launch (split order), the first DISP workgroup of a merged launch (it has waited for them)
+    // workgroups' launch (xb_roles 2), the first DISP workgroup of a merged launch (it has waited for them)
     frame_records<T>(a, reinterpret_cast<unsigned*>(smem), tid, merged_launch ? bx == HB + NB : bx == HB, rec_total, rec_id);
 }
 
@@ -1750,9 +1596,6 @@ __global__ void __launch_bounds__(T, (T == 512 ? 4 : 1)) k_xpass_disp(const Fram
     c32* fbuf = reinterpret_cast<c32*>(smem);
     const int tid = threadIdx.x;
     const int tile = blockIdx.y;
-#ifdef OCEAN_XB_TRACE
-    XbTrace xd_trace_(512);
-#endif
     constexpr int NB = (HF::NU + C - 1) / C;
     const int u0 = xcd_swizzle(blockIdx.x, NB) * C;
     start_ramp_wait(a.start_ramp, blockIdx.x, gridDim.x);   // (one 2048^2 tile: ocean_launch.h)
@@ -1855,13 +1698,9 @@ OCEAN_GEO(4096, 1024, OCEAN_R(8, 8, 8, 8), 2, 512, Plan<4096>)
 #undef OCEAN_GEO
 
 // Threads and radix plan of the single-transform z pass (k_zpass_c1): one first-stage butterfly per thread.  The shipped form runs the tile
-// size's radix-8 plan with N / 8 threads; developer builds can run the radix-16 plan of fft_engine.h with N / 16 threads from a tile size up
-// (-DOCEAN_C1_R16_MIN=2048: one exchange and two barriers less per transform, a quarter fewer twiddle products, half the waves;
-// profiles/r06_zpass_experiments.txt).
-#ifndef OCEAN_C1_R16_MIN
-#define OCEAN_C1_R16_MIN 8192
-#endif
-template <int N> constexpr bool zpass_c1_r16() { return N >= OCEAN_C1_R16_MIN && N >= 2048; }
+// size's radix-8 plan with N / 8 threads; round 6 measured the radix-16 plan of fft_engine.h with N / 16 threads from 2048 up (one exchange
+// and two barriers less per transform, a quarter fewer twiddle products, half the waves; profiles/r06_zpass_experiments.txt): no shipped size.
+template <int N> constexpr bool zpass_c1_r16() { return N >= 8192; }
 template <int N> constexpr int zpass_c1_threads() { return zpass_c1_r16<N>() ? N / 16 : N / 8; }
 template <int N> struct C1Plan { using type = std::conditional_t<zpass_c1_r16<N>(), Plan<N>, typename Geo<N>::PR>; };
 

@@ -122,46 +122,18 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
         ramp_b = ramp_ticks(bpt[1] - 4, (hb_b + nb) * tiles, c->occ_b, alone ? 1.0 : tu.ramp_pipelined_x);
         ramp_d = ramp_ticks(bpt[2], nb * tiles, c->occ_d, alone ? 1.0 : tu.ramp_pipelined_x);
     }
-    [[maybe_unused]] const bool ramp = ramp_z || ramp_b || ramp_d;
-#ifdef OCEAN_DEVELOPER      // A/B builds only: the shipped library reads no environment
-    {   static const char* const rz = getenv("OCEAN_RAMP_Z"); static const char* const rb = getenv("OCEAN_RAMP_B"); static const char* const rd = getenv("OCEAN_RAMP_D");
-        static const char* const ra = getenv("OCEAN_RAMP_ANY");     // 1: every size and batch
-        const bool on = ramp || (ra && atoi(ra) == 1);
-        if (rz && on) ramp_z = atoi(rz);
-        if (rb && on) ramp_b = atoi(rb);
-        if (rd && on) ramp_d = atoi(rd); }
-#endif
-#ifdef OCEAN_STAMPS
-    // diagnostic: stamps are recorded for ONE kernel of the frame (env OCEAN_DEBUG_STAMP_KERNEL = 0, 1, 2)
-    static unsigned long long* null_ptr = nullptr;
-    const int stamp_k = getenv("OCEAN_DEBUG_STAMP_KERNEL") ? atoi(getenv("OCEAN_DEBUG_STAMP_KERNEL")) : 0;
-    auto arm = [&](int k) {
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(ocean::g_stamps), (k == stamp_k && c->stamps) ? &c->stamps : &null_ptr,
-                                     sizeof(c->stamps), 0, hipMemcpyHostToDevice, st);
-    };
-    arm(0);
-#endif
     // the form of the z pass (see above); the usual form of the spectrum (fp32 h0, 16-bit dispersion) has instantiations without the
     // other forms' code (FAST)
     bool c1 = HASC1 && zpass_c1_pays<N>(stream_maps, tiles);
     bool zw2 = HAS2 && !c1 && (stream_maps & 4);
-#ifdef OCEAN_DEVELOPER      // A/B builds only: the shipped library reads no environment
-    static const char* const c1_env = getenv("OCEAN_ZC1");                  // 0 / 1
-    if (c1_env && HASC1) c1 = atoi(c1_env) != 0;
-    zw2 = HAS2 && !c1 && (stream_maps & 4);
-    static const char* const zw_env = getenv("OCEAN_ZW");                   // 1 or 2
-    if (zw_env && HAS2 && !c1) zw2 = atoi(zw_env) == 2;
-#endif
-    // Frame order: z pass (four transforms per column) -> k_xpass_b (HEIGHT + NORMAL workgroups) -> k_xpass_disp.  Developer builds can run
-    // the SPLIT order of profiles/r05_4096_experiments.txt instead (OCEAN_FRAME_ORDER=2: z pass {height, pair 0} -> HEIGHT workgroups ->
-    // k_xpass_disp -> z pass {pair 1, pair 2} -> NORMAL workgroups; bit-identical, slower at every size -- the x passes sit on the map write
-    // stream, not on their reads, and the second animation of the spectrum is paid in full); the per-launch fields it needs (zmask, xb_roles,
-    // rec_mode) are part of every launch.
-    bool split = false;
-#ifdef OCEAN_DEVELOPER
-    {   const char* const fo = getenv("OCEAN_FRAME_ORDER");       // (read per frame: tools/ab_order.py flips it between passes)
-        split = fo && atoi(fo) == 2 && (c1 || zw2) && (a.mode == 0 || a.mode == 1); }
-#endif
+    // a SERIAL frame's fp32 intermediates go out write-through where that form exists (ocean_kernels.h: store_z, zpass_has_wt)
+    constexpr bool HAS_WT = HASC1 && zpass_has_wt<N>();
+    const bool wt_frame = HAS_WT && alone && !(stream_maps & (4 | 8)) && c->z_write_through;
+    bool z_wt = c1 && wt_frame;
+    // Frame order: z pass (four transforms per column) -> k_xpass_b (HEIGHT + NORMAL workgroups) -> k_xpass_disp.  (Round 5 also ran a SPLIT
+    // order -- z pass {height, pair 0} -> HEIGHT workgroups -> k_xpass_disp -> z pass {pair 1, pair 2} -> NORMAL workgroups: bit-identical, slower
+    // at every size -- the x passes sit on the map write stream, not on their reads, and the second animation of the spectrum is paid in full;
+    // profiles/r05_4096_experiments.txt.  The per-launch fields it needed -- zmask, xb_roles, rec_mode -- are still part of every launch.)
     // Merged x pass (round 5): HEIGHT, NORMAL and DISP workgroups in ONE launch of k_xpass_b (xb_roles = 7) instead of k_xpass_b + k_xpass_disp.
     // The DISP workgroups transform pair 0 at once and wait for the tile's HEIGHT workgroups only before their stores (raw heights handed over
     // write-through, ocean_kernels.h: store_wt / wait_counter): a small single tile is three short DEPENDENT latency chains
@@ -171,12 +143,8 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
     // Where it pays (profiles/r05_small_tile_experiments.txt): a SERIAL frame only up to 128^2 (64^2: 12.8 -> 11.6 us; from 256^2 up the
     // hand-off's three dependent memory round trips cost more than the kernel boundary they replace: 512^2 16.6 -> 18.2 us); PIPELINED frames
     // of one tile up to 512^2, which are bound by the rate of launches, not by any kernel (512^2, depth 4: 13.2-14.9 -> 8.0 us per frame).
-    bool merged_x = xmerge_pays<N>(alone) && tiles == 1 && a.mode != 3 && !split && c->merged_x &&
+    bool merged_x = xmerge_pays<N>(alone) && tiles == 1 && a.mode != 3 && c->merged_x &&
                     (hb_b + 2u * nb) <= c->tune.handoff_wg_per_cu * cus;
-#ifdef OCEAN_DEVELOPER
-    {   const char* const xm = getenv("OCEAN_XMERGE");            // 0 / 1: force (any size, any batch; still not the Jacobian mode)
-        if (xm) merged_x = atoi(xm) != 0 && a.mode != 3 && !split; }
-#endif
     // ONE launch for the whole frame (k_frame; round 5): pipelined frames of one tile up to 128^2 in the usual form (fp32 spectrum with 16-bit
     // dispersion, fp32 intermediates, both maps streamed, not the Jacobian mode) -- they are bound by the rate of launches.  Measured at depth 4,
     // us per frame, three launches / merged x pass / one launch: 64^2 11.5 / 7.6 / 3.9, 128^2 15.0 / 10.3 / 5.2 -- and 256^2 8.2-15.4 / 5.8 / 8.3,
@@ -185,11 +153,32 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
     constexpr bool HAS_ONE = (N <= 128 || (DEV && N <= 512)) && G::T_ROWS == G::T_C;      // (developer builds: up to 512^2, for the A/B of that log)
     // (like the merged x pass only where every workgroup of the grid has a slot at once -- one per compute unit, the regime the hand-off recipe is
     //  measured for: forward progress then never depends on the order in which workgroups are dispatched)
-    [[maybe_unused]] bool one_launch = HAS_ONE && !alone && tiles == 1 && a.mode <= 2 && fast && (stream_maps & 15) == 3 && !split && c->merged_x &&
-                                       ((unsigned)(N / 2 + 1) + hb_b + 2u * nb) <= c->tune.handoff_wg_per_cu * cus;
-#ifdef OCEAN_DEVELOPER
-    {   const char* const ol = getenv("OCEAN_ONE_LAUNCH");        // 0 / 1 (the form's own preconditions still hold)
-        if (ol) one_launch = one_launch && atoi(ol) != 0; }
+    bool one_launch = HAS_ONE && !alone && tiles == 1 && a.mode <= 2 && fast && (stream_maps & 15) == 3 && c->merged_x &&
+                      ((unsigned)(N / 2 + 1) + hb_b + 2u * nb) <= c->tune.handoff_wg_per_cu * cus;
+    // the DISP workgroups of a merged launch poll the HEIGHT count; beside other chains' launches a poll every ~3 us instead of back to back
+    // takes the pollers off the memory system (512^2 depth 4: 7.66-7.97 -> 7.35-7.55 us per frame, 256^2 7.8-9.7 -> 7.2-7.3); a serial frame
+    // (<= 128^2) keeps the tight poll -- there the wait IS the frame's latency -- and so does a one-launch frame
+    int poll_sleep = (merged_x && !one_launch && !alone) ? 1 : 0;
+#ifdef OCEAN_DEVELOPER      // A/B builds only: the shipped library reads no environment.  Every override of the rules above, in their order
+    {   static const char* const c1_env = getenv("OCEAN_ZC1");                  // 0 / 1
+        if (c1_env && HASC1) c1 = atoi(c1_env) != 0;
+        zw2 = HAS2 && !c1 && (stream_maps & 4);
+        static const char* const zw_env = getenv("OCEAN_ZW");                   // 1 or 2
+        if (zw_env && HAS2 && !c1) zw2 = atoi(zw_env) == 2;
+        const char* const wt_env = getenv("OCEAN_Z_WT");          // 0: off (read per frame: A/B inside one process)
+        z_wt = c1 && wt_frame && !(wt_env && atoi(wt_env) == 0);
+        const char* const xm = getenv("OCEAN_XMERGE");            // 0 / 1: force (any size, any batch; still not the Jacobian mode)
+        if (xm) merged_x = atoi(xm) != 0 && a.mode != 3;
+        const char* const ol = getenv("OCEAN_ONE_LAUNCH");        // 0 / 1 (the form's own preconditions still hold)
+        if (ol) one_launch = one_launch && atoi(ol) != 0;
+        const char* const ps = getenv("OCEAN_POLL_SLEEP");
+        poll_sleep = ps ? atoi(ps) : (merged_x && !one_launch && !alone) ? 1 : 0;
+        static const char* const rz = getenv("OCEAN_RAMP_Z"); static const char* const rb = getenv("OCEAN_RAMP_B"); static const char* const rd = getenv("OCEAN_RAMP_D");
+        static const char* const ra = getenv("OCEAN_RAMP_ANY");     // 1: every size and batch
+        const bool on = ramp_z || ramp_b || ramp_d || (ra && atoi(ra) == 1);
+        if (rz && on) ramp_z = atoi(rz);
+        if (rb && on) ramp_b = atoi(rb);
+        if (rd && on) ramp_d = atoi(rd); }
 #endif
     c->handoff = merged_x || one_launch;      // (what recover_fault re-runs without a hand-off, should one of this frame's in-launch waits give up)
     int launches = 0;
@@ -200,19 +189,16 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
         return m;
     };
     const int rec_last = a.rec_mode;                         // what the frame's LAST launch does with the completion records (ocean_api.hip)
-    auto launch_z = [&](int zmask) -> hipError_t {
-        unsigned gx = zw2 ? N / 4 + 1 : N / 2 + 1;
+    auto launch_z = [&]() -> hipError_t {
+        const unsigned gx = zw2 ? N / 4 + 1 : N / 2 + 1;
         FrameArgs za = a;
-        za.zmask = zmask; za.rec_mode = 0;
+        za.rec_mode = 0;
         // one 2048^2 tile: the single-transform form's 1025 workgroups are one resident round -- staggered start (start_ramp_wait)
         za.start_ramp = c1 ? ramp_z : 0;
-#if defined(OCEAN_STAMPS) || defined(OCEAN_DEVELOPER)
-        if (const char* ev = getenv("OCEAN_DEBUG_ROWS_GRID")) gx = (unsigned)atoi(ev);   // diagnostic: partial grid (results wrong)
-#endif
         const unsigned threads = c1 ? (unsigned)zpass_c1_threads<N>() : (unsigned)G::T_ROWS;
         const size_t lds = c1 ? zpass_c1_lds_bytes<N>() : (zw2 ? lds_rows2 : lds_rows);
         const dim3 grid(gx, tiles), block(threads);
-        if (launches == 0) {
+        {
             ocean_launch_info& li = c->last_launch[0];
             li.tile_size = N; li.grid_x = gx; li.grid_y = tiles; li.block = threads; li.mode = (uint32_t)a.mode;
             li.per_workgroup = zw2 ? 2u : 1u;
@@ -220,7 +206,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
             li.flags = ((stream_maps & 4) ? OCEAN_LAUNCH_NT_INTER : 0u) | ((stream_maps & 8) ? OCEAN_LAUNCH_HALF_INTER : 0u) |
                        (a.mode == 3 ? OCEAN_LAUNCH_JACOBIAN : 0u) | (a.h0h ? OCEAN_LAUNCH_FP16_SPECTRUM : 0u) |
                        (a.omega_q ? 0u : OCEAN_LAUNCH_FP32_DISPERSION) | (c1 ? OCEAN_LAUNCH_SINGLE_TRANSFORM : 0u) |
-                       (za.start_ramp ? OCEAN_LAUNCH_STAGGERED_START : 0u) | (split ? OCEAN_LAUNCH_SPLIT_ORDER : 0u);
+                       (za.start_ramp ? OCEAN_LAUNCH_STAGGERED_START : 0u) | (z_wt ? OCEAN_LAUNCH_WT_INTER : 0u);
         }
         hipEvent_t* mz = next_marks(0);
 #ifdef OCEAN_CLOCKPROBE
@@ -230,17 +216,11 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
         }
 #endif
         bool launched = false;
-        // a SERIAL frame's fp32 intermediates go out write-through where that form exists (ocean_kernels.h: store_z, zpass_has_wt)
-        if constexpr (HASC1 && zpass_has_wt<N>()) {
-            bool wt = c1 && alone && !(stream_maps & (4 | 8)) && c->z_write_through;
-#ifdef OCEAN_DEVELOPER
-            if (const char* ev = getenv("OCEAN_Z_WT")) wt = wt && atoi(ev) != 0;     // (read per frame: A/B inside one process)
-#endif
-            if (wt) {
+        if constexpr (HAS_WT) {
+            if (z_wt) {
                 if (fast) launch(k_zpass_c1<N, zpass_c1_threads<N>(), typename C1Plan<N>::type, false, false, true, true>, grid, block, lds, st, mz, za);
                 else launch(k_zpass_c1<N, zpass_c1_threads<N>(), typename C1Plan<N>::type, false, false, false, true>, grid, block, lds, st, mz, za);
                 launched = true;
-                if (launches == 1) c->last_launch[0].flags |= OCEAN_LAUNCH_WT_INTER;
             }
         }
 #define OCEAN_ZPASS3(znt, z16, fast) \
@@ -267,60 +247,42 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
 #define OCEAN_XPASS(kern, grid, lds, ev, nts, args)                                                                 \
         do { if (stream_maps & 8) OCEAN_XPASS2(kern, grid, lds, ev, nts, true, args);                                 \
              else OCEAN_XPASS2(kern, grid, lds, ev, nts, false, args); } while (0)
-    auto launch_xb = [&](int roles, int rec_mode) {
-        dim3 gb((roles & 1 ? hb : 0u) + (roles & 2 ? nb : 0u) + (roles & 4 ? nb : 0u), tiles);
-#ifdef OCEAN_XBGRID
-        if (const char* ev = getenv("OCEAN_DEBUG_XB_GRID")) gb.x = (unsigned)atoi(ev);   // diagnostic: partial grid (results wrong)
-#endif
-        if (roles & 2) {
+    auto launch_xb = [&](bool merged) {      // HEIGHT + NORMAL workgroups; merged: the DISP workgroups as well -- then the frame's last launch
+        const dim3 gb(hb + nb + (merged ? nb : 0u), tiles);
+        {
             ocean_launch_info& li = c->last_launch[1];
             li.tile_size = N; li.grid_x = gb.x; li.grid_y = tiles; li.block = G::T_C; li.mode = (uint32_t)a.mode;
             li.per_workgroup = C;
             li.lds_bytes = (uint32_t)lds_b;
             li.flags = ((stream_maps & 1) ? OCEAN_LAUNCH_NT_MAPS : 0u) | ((stream_maps & 8) ? OCEAN_LAUNCH_HALF_INTER : 0u) |
-                       (jac ? OCEAN_LAUNCH_JACOBIAN : 0u) | (ramp_b ? OCEAN_LAUNCH_STAGGERED_START : 0u) | (split ? OCEAN_LAUNCH_SPLIT_ORDER : 0u) |
-                       ((roles & 4) ? OCEAN_LAUNCH_MERGED_X : 0u);
-            if (roles & 4) {                     // no k_xpass_disp this frame: its record describes the launch that did its work
+                       (jac ? OCEAN_LAUNCH_JACOBIAN : 0u) | (ramp_b ? OCEAN_LAUNCH_STAGGERED_START : 0u) |
+                       (merged ? OCEAN_LAUNCH_MERGED_X : 0u);
+            if (merged) {                        // no k_xpass_disp this frame: its record describes the launch that did its work
                 c->last_launch[2] = li;
                 c->last_launch[2].flags = (li.flags & ~(uint32_t)OCEAN_LAUNCH_NT_MAPS) | ((stream_maps & 2) ? OCEAN_LAUNCH_NT_MAPS : 0u);
             }
         }
         hipEvent_t* mb = next_marks(1);
-#ifdef OCEAN_XB_TRACE
-        {   // diagnostic: this translation unit's copy of the trace pointer, set when the context's buffer changes (not per frame)
-            static unsigned long long* armed = nullptr;
-            if (armed != c->stamps) { armed = c->stamps; (void)hipMemcpyToSymbol(HIP_SYMBOL(ocean::g_xb_trace), &armed, sizeof(armed)); }
-        }
-#endif
         FrameArgs ba = a;
-        ba.xb_roles = roles; ba.rec_mode = rec_mode;
-        // the DISP workgroups of a merged launch poll the HEIGHT count; beside other chains' launches a poll every ~3 us instead of back to back
-        // takes the pollers off the memory system (512^2 depth 4: 7.66-7.97 -> 7.35-7.55 us per frame, 256^2 7.8-9.7 -> 7.2-7.3); a serial frame
-        // (<= 128^2) keeps the tight poll -- there the wait IS the frame's latency
-        ba.poll_sleep = ((roles & 4) && !alone) ? 1 : 0;
-#ifdef OCEAN_DEVELOPER
-        if (const char* ps = getenv("OCEAN_POLL_SLEEP")) ba.poll_sleep = atoi(ps);
-#endif
+        ba.xb_roles = merged ? 7 : 3; ba.rec_mode = merged ? rec_last : 0;
+        ba.poll_sleep = poll_sleep;
         ba.start_ramp = ramp_b;             // over its normal-map workgroups (the height workgroups start at once)
         if (stream_maps & 1) OCEAN_XPASS(k_xpass_b, gb, lds_b, mb, true, ba);
         else OCEAN_XPASS(k_xpass_b, gb, lds_b, mb, false, ba);
     };
-    auto launch_xd = [&](int rec_mode) {
-        dim3 gd(nb, tiles);
-#ifdef OCEAN_XBGRID
-        if (const char* ev = getenv("OCEAN_DEBUG_XD_GRID")) gd.x = (unsigned)atoi(ev);
-#endif
+    auto launch_xd = [&]() {
+        const dim3 gd(nb, tiles);
         {
             ocean_launch_info& li = c->last_launch[2];
             li.tile_size = N; li.grid_x = gd.x; li.grid_y = tiles; li.block = G::T_C; li.mode = (uint32_t)a.mode;
             li.per_workgroup = C;
             li.lds_bytes = (uint32_t)lds_m;
             li.flags = ((stream_maps & 2) ? OCEAN_LAUNCH_NT_MAPS : 0u) | ((stream_maps & 8) ? OCEAN_LAUNCH_HALF_INTER : 0u) |
-                       (jac ? OCEAN_LAUNCH_JACOBIAN : 0u) | (ramp_d ? OCEAN_LAUNCH_STAGGERED_START : 0u) | (split ? OCEAN_LAUNCH_SPLIT_ORDER : 0u);
+                       (jac ? OCEAN_LAUNCH_JACOBIAN : 0u) | (ramp_d ? OCEAN_LAUNCH_STAGGERED_START : 0u);
         }
         hipEvent_t* md = next_marks(2);
         FrameArgs da = a;
-        da.rec_mode = rec_mode;
+        da.rec_mode = rec_last;
         da.start_ramp = ramp_d;             // its 257 workgroups are one per CU: the same read-then-write burst
         if (stream_maps & 2) OCEAN_XPASS(k_xpass_disp, gd, lds_m, md, true, da);
         else OCEAN_XPASS(k_xpass_disp, gd, lds_m, md, false, da);
@@ -334,12 +296,9 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
                 c->attr_one_n = (uint32_t)N;
             }
             FrameArgs fa = a;
-            fa.zmask = 15; fa.xb_roles = 7; fa.rec_mode = rec_last; fa.start_ramp = 0;
+            fa.xb_roles = 7; fa.rec_mode = rec_last; fa.start_ramp = 0;
             fa.zdone_target = (++c->zgen[c->cur_set]) * (unsigned)(N / 2 + 1);
-            fa.poll_sleep = 0;
-#ifdef OCEAN_DEVELOPER
-            if (const char* ps = getenv("OCEAN_POLL_SLEEP")) fa.poll_sleep = atoi(ps);
-#endif
+            fa.poll_sleep = poll_sleep;
             const dim3 grid((N / 2 + 1) + hb_b + 2 * nb, tiles), block(G::T_C);
             for (int k = 0; k < 3; ++k) {
                 ocean_launch_info& li = c->last_launch[k];
@@ -354,31 +313,15 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
             return hipGetLastError();
         }
     }
-    if (!split) {
-        if ((e = launch_z(15)) != hipSuccess) return e;
-        if (c->after_z && (e = hipEventRecord(c->after_z, st)) != hipSuccess) return e;   // the first frames after a drain: the next chain's z pass starts behind this one (ocean_api.hip)
-#ifdef OCEAN_STAMPS
-        if (getenv("OCEAN_DEBUG_ONLY_ZPASS")) return hipGetLastError();
-        arm(1);
-#endif
-        if (merged_x) {
-            launch_xb(7, rec_last);
-        } else {
-            launch_xb(3, 0);
-            // the normal map is final behind this launch: ocean_compute_waves_read starts its device-to-host copy here, beside the displacement pass
-            if (c->after_b) { if ((e = hipEventRecord(c->after_b, st)) != hipSuccess) return e; c->after_b_recorded = true; }
-#ifdef OCEAN_STAMPS
-            arm(2);
-#endif
-            launch_xd(rec_last);
-        }
+    if ((e = launch_z()) != hipSuccess) return e;
+    if (c->after_z && (e = hipEventRecord(c->after_z, st)) != hipSuccess) return e;   // the first frames after a drain: the next chain's z pass starts behind this one (ocean_api.hip)
+    if (merged_x) {
+        launch_xb(true);
     } else {
-        if ((e = launch_z(8 | 1)) != hipSuccess) return e;
-        if (c->after_z && (e = hipEventRecord(c->after_z, st)) != hipSuccess) return e;
-        launch_xb(1, 0);
-        launch_xd(rec_last == 1 ? 1 : 0);                   // (early records may go out here: the height keys are final; counted ones come from the last launch)
-        if ((e = launch_z(2 | 4)) != hipSuccess) return e;
-        launch_xb(2, rec_last == 2 ? 2 : 0);
+        launch_xb(false);
+        // the normal map is final behind this launch: ocean_compute_waves_read starts its device-to-host copy here, beside the displacement pass
+        if (c->after_b) { if ((e = hipEventRecord(c->after_b, st)) != hipSuccess) return e; c->after_b_recorded = true; }
+        launch_xd();
     }
 #undef OCEAN_XPASS2
 #undef OCEAN_XPASS
