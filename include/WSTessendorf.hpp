@@ -260,6 +260,39 @@ public:
                                     reinterpret_cast<float*>(hits.data()), reinterpret_cast<float*>(normals.data())), "ocean_raycast_surface");
     }
 
+    // Beyond the reference: persistent foam (ocean_update_foam) -- whitecap coverage in [0, 1] that appears where the surface of the last
+    // ComputeWaves compresses, spreads a little and fades over seconds.  UpdateFoam(dt) applies one step of dt seconds (the library's
+    // defaults, or the caller's ocean_foam); GetFoam() returns it texel for texel beside GetDisplacements() / GetNormals(), valid until the
+    // next GetFoam(); QueryFoam gives the foam above world points on the geometry of QuerySurface: out[i] = (foam, rest x, rest z, residual).
+    void UpdateFoam(float dt, const ocean_foam* foamOrNull = nullptr)
+    {
+        ocean_foam f;
+        ocean_default_foam(&f);
+        if (foamOrNull) f = *foamOrNull;
+        if (m_Pending) Wait();
+        Check(ocean_update_foam(m_Ctx, 0, &f, dt), "ocean_update_foam");
+    }
+    const std::vector<float>& GetFoam()
+    {
+        const size_t n = ocean_tile_size(m_Ctx);
+        m_Foam.resize(n * n);
+        Check(ocean_read_foam(m_Ctx, 0, m_Foam.data()), "ocean_read_foam");
+        return m_Foam;
+    }
+    void QueryFoam(const std::vector<vec2>& xz, std::vector<vec4>& out, uint32_t iterations = 8)
+    {
+        ocean_surface s{};
+        s.first_tile = 0; s.cascades = 1;
+        s.grid_size = ocean_tile_size(m_Ctx);
+        s.vertex_distance = s_kDefaultTileLength / (float)s_kDefaultTileSize;
+        s.choppy = GetDisplacementLambda();
+        s.iterations = iterations;
+        s.uv_scales[0] = 1.0f;
+        out.resize(xz.size());
+        Check(ocean_query_foam(m_Ctx, &s, reinterpret_cast<const float*>(xz.data()), (uint32_t)xz.size(),
+                               reinterpret_cast<float*>(out.data())), "ocean_query_foam");
+    }
+
 private:
     bool Pin(int i)
     {
@@ -292,6 +325,7 @@ private:
     ocean_params m_Params{};
     std::vector<Displacement> m_Displacements[2];     // [m_Front]: what the getters return; the other pair: ComputeWavesAsync's target
     std::vector<Normal> m_Normals[2];
+    std::vector<float> m_Foam;                        // what GetFoam() returned last
     int m_Front{ 0 };
     bool m_Pending{ false };                          // a ComputeWavesAsync whose copy has not been waited for
     bool m_Tracking{ false };                         // asynchronous frames leave completion records (ocean_set_frame_tracking)

@@ -141,6 +141,64 @@ int ocean_raycast_surface(ocean_t* ctx, const ocean_surface* s, const ocean_rayc
 int ocean_raycast_surface_device(ocean_t* ctx, const ocean_surface* s, const ocean_raycast* r,
                                  const void* d_rays, uint32_t count, void* d_out_hit, void* d_out_nrm);
 
+/* ---- persistent foam: whitecap coverage accumulated across frames -----------------------------------------------------
+ * The reference's to-do "Foam rendering" (README.md:37-44).  Its fragment shader paints the Jacobian slot white where it is
+ * negative: an instantaneous, binary mask.  Here the same signal feeds a coverage field with memory, F[tiles][N][N] of float
+ * in [0, 1], in the texel layout of the maps (row m = image row), owned by the context: foam appears where the surface
+ * compresses, spreads a little and fades over seconds.  It lives in texture (rest) space: drawn through the vertex stage at
+ * the vertex's uv it moves with the choppy displacement by construction.  A renderer samples it as a third texture beside
+ * the two maps (max over cascades); game code asks for it at world points (ocean_query_foam).
+ * One step, for texel (m, n) of a tile, indices wrapped by & (N - 1) (REPEAT, like the sampler); fp32 throughout, no
+ * contraction, in exactly this order (the test suite repeats it step for step):
+ *   J     Jacobian of the texel, from what the frame that wrote the maps computed (its mode is recorded when it is enqueued):
+ *           OCEAN_MODE_JACOBIAN frame:  J = disp.w
+ *           OCEAN_MODE_FULL7 frame:     J = (1.0f + lam * nrm.z) * (1.0f + lam * nrm.w), lam the lambda of that tile's frame
+ *                                       (the diagonal Jacobian the vertex normal and the surface query use)
+ *           CHOPPY5 / HEIGHT1 frame:    OCEAN_E_UNSUPPORTED (the ingredients are not in the maps)
+ *   decay = (float)exp(-(double)dt / (double)lifetime), rounded once on the host
+ *   g    = fminf(fmaxf((threshold - J) * gain, 0.0f), 1.0f)
+ *   r(k) = (F[k][n-1] + 2.0f * F[k][n]) + F[k][n+1]              for k = m-1, m, m+1
+ *   b    = ((r(m-1) + 2.0f * r(m)) + r(m+1)) * 0.0625f           (3 x 3 binomial)
+ *   s    = F[m][n] + spread * (b - F[m][n])
+ *   c    = s * decay
+ *   f    = fmaxf(c, g);   F'[m][n] = (f < cutoff) ? 0.0f : f
+ * cutoff keeps the field sparse and the spreading tail out of the denormal range; cutoff = 0 disables it.
+ * ocean_update_foam applies one step to `tile` (or OCEAN_ALL_TILES: one launch for all of them; the other tiles keep their
+ * state) from the most recently enqueued frame (caller-bound or imported output where it is), enqueued behind that frame on
+ * its stream and ordered with the other consumers, so updates at pipeline depth > 1 are ordered among themselves.  Calling
+ * it twice behind one frame applies two steps.  Two buffers of tiles * N * N floats are allocated on first use
+ * (OCEAN_E_NOMEM leaves nothing behind) and alternate: ocean_device_foam hands out the one that holds the state after the
+ * most recently enqueued update -- ask again after each update -- and NULL while there is none.  ocean_read_foam copies one
+ * tile out (synchronises).  ocean_prepare zeroes the state (not ready until the next update), ocean_set_tile_size frees it,
+ * ocean_reset_foam zeroes it stream-ordered (a ready state stays ready; nothing to do before the first update).
+ * An update enqueued behind a frame whose in-launch wait gives up has consumed that frame: the call that recovers reports
+ * OCEAN_E_HIP once (ocean.h), and the state then contains one step taken from a faulted frame -- reset it or let it fade.
+ * ocean_query_foam: for each world point q the K Newton steps of ocean_query_surface on the same ocean_surface give the rest
+ * point r = r_K; tile c's foam is sampled at (u, v) * uv_scales[c] (LINEAR, REPEAT; (c00*ia + c10*a)*ib + (c01*ia + c11*a)*b)
+ * and the cascades are combined with fmaxf from 0.0f in cascade order (the counterpart of w = min_c D_c.w):
+ *   out[i] = (foam, r.x, r.z, |P(r).xz - q|)
+ * r is the texture-space coordinate a caller needs for anything else it samples there.  Host / device variants as
+ * ocean_query_surface / _device (a staging buffer that grows on demand; or enqueue and return, d_out 16-byte aligned).
+ * Errors: OCEAN_E_INVALID for a NULL context, params or destination, a tile outside the batch, lifetime <= 0, spread or
+ * cutoff outside [0, 1], a non-finite field or dt, dt < 0, the invalid ocean_surface cases of ocean_query_surface;
+ * OCEAN_E_NOT_READY for an update without Prepare or frame, a read or query without an update since Prepare.
+ * points == 0 does nothing and returns OCEAN_OK.  (An addition to ABI version 5.)                                      */
+typedef struct ocean_foam {
+    float threshold;                   /* foam is generated where J < threshold                      default 0.6    */
+    float gain;                        /* generation = clamp((threshold - J) * gain, 0, 1)           default 2.5    */
+    float lifetime;                    /* e-folding time in seconds, > 0                             default 4.0    */
+    float spread;                      /* 0 .. 1, blend towards the 3 x 3 binomial per step          default 0.25   */
+    float cutoff;                      /* 0 .. 1, values below it become 0                           default 1/1024 */
+} ocean_foam;
+
+void ocean_default_foam(ocean_foam* f);
+int ocean_update_foam(ocean_t* ctx, uint32_t tile /* or OCEAN_ALL_TILES */, const ocean_foam* f, float dt);
+int ocean_reset_foam(ocean_t* ctx);
+int ocean_read_foam(ocean_t* ctx, uint32_t tile, float* out /* N * N */);
+int ocean_device_foam(ocean_t* ctx, void** d_foam /* [tiles][N][N] */);
+int ocean_query_foam(ocean_t* ctx, const ocean_surface* s, const float* xz, uint32_t points, float* out /* 4 * points */);
+int ocean_query_foam_device(ocean_t* ctx, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -320,6 +320,60 @@ class OceanBatch:
         _abi.check(self._L.ocean_raycast_surface_device(self._h, C.byref(s), C.byref(r), C.c_void_p(d_rays), int(count),
                                                         C.c_void_p(d_hit), C.c_void_p(d_nrm)), "ocean_raycast_surface_device")
 
+    # -- persistent foam (include/ocean_consumers.h: ocean_update_foam ...) ---------------------------------------------
+    @staticmethod
+    def foam_params(**params) -> "_abi.Foam":
+        """struct ocean_foam with the library's defaults (ocean_default_foam), patched by threshold / gain / lifetime / spread / cutoff."""
+        f = _abi.Foam()
+        _abi.lib().ocean_default_foam(C.byref(f))
+        for k, v in params.items():
+            if k not in ("threshold", "gain", "lifetime", "spread", "cutoff"):
+                raise TypeError(f"unknown foam parameter {k!r}")
+            setattr(f, k, float(v))
+        return f
+
+    def update_foam(self, dt: float, tile: int = _abi.OCEAN_ALL_TILES, **params):
+        """One foam step of dt seconds behind the most recent frame (ocean_update_foam), for one tile or all of them: generated where the
+        frame's Jacobian is under `threshold`, blended towards the 3 x 3 binomial by `spread`, faded with `lifetime`.  Enqueued; returns at once."""
+        f = self.foam_params(**params)
+        _abi.check(self._L.ocean_update_foam(self._h, tile, C.byref(f), dt), "ocean_update_foam")
+
+    def reset_foam(self):
+        _abi.check(self._L.ocean_reset_foam(self._h), "ocean_reset_foam")
+
+    def read_foam(self, tile: int = 0) -> np.ndarray:
+        """Foam coverage of `tile` after the most recent update: (N, N) float32 in [0, 1], in the maps' texel layout (synchronises)."""
+        n = self.tile_size
+        out = np.empty((n, n), dtype=np.float32)
+        _abi.check(self._L.ocean_read_foam(self._h, tile, out.ctypes.data_as(C.c_void_p)), "ocean_read_foam")
+        return out
+
+    def device_foam(self) -> Optional[int]:
+        """Device address of the foam [tiles][N][N] after the most recently enqueued update (ask again after each update), None before any."""
+        p = C.c_void_p()
+        _abi.check(self._L.ocean_device_foam(self._h, C.byref(p)), "ocean_device_foam")
+        return p.value
+
+    def query_foam(self, xz, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                   vertex_distance: Optional[float] = None, choppy: float = -1.0, iterations: int = 8):
+        """Foam above each world point xz [points, 2] (ocean_query_foam), on the surface query_surface defines: returns (points, 4)
+        float32 rows (foam, rest x, rest z, residual |P(rest).xz - xz| in metres); foam is the largest of the cascades' samples."""
+        q = np.ascontiguousarray(xz, dtype=np.float32).reshape(-1, 2)
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        out = np.empty((q.shape[0], 4), dtype=np.float32)
+        _abi.check(self._L.ocean_query_foam(self._h, C.byref(s), q.ctypes.data_as(C.c_void_p), q.shape[0],
+                                            out.ctypes.data_as(C.c_void_p)), "ocean_query_foam")
+        return out
+
+    def query_foam_device(self, d_xz: int, points: int, d_out: int, first_tile: int = 0, uv_scales=(1.0,),
+                          grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0,
+                          iterations: int = 8):
+        """query_foam on device arrays of the context's device (ocean_query_foam_device): d_xz [points][2], d_out [points][4] float32.
+        Enqueued on the frame's stream (`stream`); returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        _abi.check(self._L.ocean_query_foam_device(self._h, C.byref(s), C.c_void_p(d_xz), int(points), C.c_void_p(d_out)),
+                   "ocean_query_foam_device")
+
     def build_mips(self, tile: int = 0):
         """Mip chain of both maps of `tile` (ocean_build_mips: the reference's s_kUseMipMapping path, Texture2D.cpp:228-330):
         returns (disp_levels, nrm_levels), lists of (N >> l, N >> l, 4) float32 arrays for l = 1 .. log2 N."""
@@ -621,3 +675,22 @@ class WSTessendorf:
             normals[...] = nrm.reshape(normals.shape)
             nrm = normals
         return hit, nrm
+
+    # -- beyond the reference: persistent foam (include/WSTessendorf.hpp: UpdateFoam / GetFoam / QueryFoam) -----------------
+    def UpdateFoam(self, dt: float, **params):
+        """One foam step of dt seconds behind the last ComputeWaves (ocean_update_foam; the library's defaults unless given)."""
+        self._b.update_foam(dt, 0, **params)
+
+    def GetFoam(self) -> np.ndarray:
+        """Foam coverage (N, N) float32 in [0, 1], texel for texel beside GetDisplacements() / GetNormals()."""
+        return self._b.read_foam(0)
+
+    def QueryFoam(self, xz, out: np.ndarray | None = None, iterations: int = 8):
+        """Foam above each world point xz [points, 2] (ocean_query_foam) on the geometry of QuerySurface.  Fills out [points, 4] float32
+        when given, and returns it: (foam, rest x, rest z, residual in metres)."""
+        res = self._b.query_foam(xz, grid_size=self._b.tile_size, vertex_distance=self.s_kDefaultTileLength / self.s_kDefaultTileSize,
+                                 choppy=self.GetDisplacementLambda(), iterations=iterations)
+        if out is not None:
+            out[...] = res.reshape(out.shape)
+            res = out
+        return res

@@ -42,6 +42,7 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_displace_grid", "ocean_displace_grid_cascades", "ocean_read_grid", "ocean_device_grid",
     "ocean_mip_texels", "ocean_build_mips", "ocean_read_mips", "ocean_device_mips",
     "ocean_query_surface", "ocean_query_surface_device", "ocean_raycast_surface", "ocean_raycast_surface_device",
+    "ocean_default_foam", "ocean_update_foam", "ocean_reset_foam", "ocean_read_foam", "ocean_device_foam", "ocean_query_foam", "ocean_query_foam_device",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
     "ocean_read_spectrum", "ocean_read_xi",
@@ -88,6 +89,11 @@ class Surface(C.Structure):
 class Raycast(C.Structure):
     """struct ocean_raycast (include/ocean_consumers.h): how far and how finely a ray cast samples each ray."""
     _fields_ = [("max_distance", C.c_float), ("steps", C.c_uint32), ("refine", C.c_uint32)]
+
+
+class Foam(C.Structure):
+    """struct ocean_foam (include/ocean_consumers.h): how the persistent foam is generated, spreads and fades."""
+    _fields_ = [("threshold", C.c_float), ("gain", C.c_float), ("lifetime", C.c_float), ("spread", C.c_float), ("cutoff", C.c_float)]
 
 
 last_build = ""      # what the most recent build() did, for the caller to log
@@ -226,6 +232,13 @@ def lib() -> C.CDLL:
         "ocean_query_surface_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_raycast_surface": (i32, [P, C.POINTER(Surface), C.POINTER(Raycast), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_raycast_surface_device": (i32, [P, C.POINTER(Surface), C.POINTER(Raycast), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_default_foam": (None, [C.POINTER(Foam)]),
+        "ocean_update_foam": (i32, [P, u32, C.POINTER(Foam), f32]),
+        "ocean_reset_foam": (i32, [P]),
+        "ocean_read_foam": (i32, [P, u32, C.c_void_p]),
+        "ocean_device_foam": (i32, [P, C.POINTER(P)]),
+        "ocean_query_foam": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p]),
+        "ocean_query_foam_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p]),
         "ocean_set_mode": (i32, [P, i32]),
         "ocean_set_dispersion": (i32, [P, i32, f32]),
         "ocean_set_spectrum_precision": (i32, [P, i32]),

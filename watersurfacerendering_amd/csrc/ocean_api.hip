@@ -16,6 +16,7 @@
 
 #include "ocean_ctx.h"
 #include "ocean_aux_kernels.h"      // this translation unit also holds the Prepare(), read-out and consumer kernels
+#include "ocean_foam_kernels.h"     //   ... and the persistent foam's
 
 using namespace ocean;
 
@@ -73,6 +74,11 @@ static void free_device(ocean_ctx* c)
     c->query_buf = nullptr; c->query_capacity = 0;
     if (c->ray_buf) (void)hipFree(c->ray_buf);
     c->ray_buf = nullptr; c->ray_capacity = 0;
+    for (float*& f : c->foam) { if (f) (void)hipFree(f); f = nullptr; }
+    if (c->foam_lambda) (void)hipFree(c->foam_lambda);
+    if (c->foam_query_buf) (void)hipFree(c->foam_query_buf);
+    c->foam_lambda = nullptr; c->foam_lambda_host.clear(); c->foam_query_buf = nullptr; c->foam_query_capacity = 0;
+    c->foam_cur = 0; c->foam_ready = false;
     c->prepared = false; c->placement_done = false;
     // nothing of the old buffers may be referred to any more: no frame, no chain to read out, no mips of the old size
     c->have_frame = false; c->last_set = 0; c->frame_ctr = 0; c->mips_ready = false; c->grid_vertices = 0;
@@ -514,6 +520,11 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
         }
         HIP_TRY(hipMemcpy(c->zscale, zs.data(), 2 * t * sizeof(float4), hipMemcpyHostToDevice));
     }
+    if (c->foam[0]) {       // the foam belongs to the sea that is replaced: zero, and not ready until the next update
+        const size_t foam_bytes = t * n2 * sizeof(float);
+        for (float* f : c->foam) HIP_TRY(hipMemsetAsync(f, 0, foam_bytes, stream_of(c, 0)));
+    }
+    c->foam_ready = false;
     SYNC_ALL(c);
     {
         unsigned overflow = 1;
@@ -689,6 +700,7 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     c->tracked[set] = track;
     c->set_lambda[set].resize(c->tiles); c->set_length[set].resize(c->tiles);
     for (uint32_t i = 0; i < c->tiles; ++i) { c->set_lambda[set][i] = c->params[i].lambda; c->set_length[set][i] = c->prep_length[i]; }
+    c->set_mode[set] = c->mode;
     c->last_t[set] = t; c->last_pipe[set] = pipelined; c->last_handoff[set] = c->handoff;
     if (pipe && !redo) c->frame_ctr++;
     c->have_frame = true;
@@ -1516,6 +1528,206 @@ int ocean_raycast_surface_device(ocean_t* c, const ocean_surface* s, const ocean
     hipStream_t st = stream_of(c, c->last_set);
     CONSUMER_BEGIN(c, st);
     { int rc_ = launch_raycast(c, a, st); if (rc_) return rc_; }
+    CONSUMER_END(c, st);
+    return OCEAN_OK;
+}
+
+}  // extern "C"
+
+// ---- persistent foam (include/ocean_consumers.h) -----------------------------------------------------------------------------------------
+// Both buffers or none (as alloc_jacobian): zero-filled on the stream of the update that asked for them.
+static int alloc_foam(ocean_ctx* c, hipStream_t st)
+{
+    if (c->foam[1]) return OCEAN_OK;               // the second of the two: complete
+    const size_t bytes = (size_t)c->tiles * c->n * c->n * sizeof(float);
+    for (int k = 0; k < 2; ++k) {
+        if (c->foam[k]) { (void)hipFree(c->foam[k]); c->foam[k] = nullptr; }       // leftovers of an earlier failed attempt
+        if (hipMalloc(&c->foam[k], bytes) != hipSuccess || hipMemsetAsync(c->foam[k], 0, bytes, st) != hipSuccess) {
+            for (int j = 0; j <= k; ++j) if (c->foam[j]) { (void)hipFree(c->foam[j]); c->foam[j] = nullptr; }
+            g_last_hip = (int)hipGetLastError();
+            return OCEAN_E_NOMEM;
+        }
+    }
+    c->foam_cur = 0; c->foam_ready = false;
+    return OCEAN_OK;
+}
+
+// Rows per band of k_foam_update's row walk: as long as the launch still has four waves for every compute unit (a band re-reads two rows of F).
+static unsigned foam_band_rows(const ocean_ctx* c, uint32_t tiles)
+{
+    const double waves_per_row = (double)tiles * c->n * c->n / 256.0;
+    unsigned rows = 32;
+    while (rows > 4 && waves_per_row / rows < 4.0 * (c->cu_count > 0 ? c->cu_count : 256)) rows /= 2;
+    return rows < c->n ? rows : c->n;
+}
+
+extern "C" {
+
+void ocean_default_foam(ocean_foam* f)
+{
+    if (!f) return;
+    f->threshold = 0.6f;
+    f->gain = 2.5f;
+    f->lifetime = 4.0f;
+    f->spread = 0.25f;
+    f->cutoff = 1.0f / 1024.0f;
+}
+
+int ocean_update_foam(ocean_t* c, uint32_t tile, const ocean_foam* f, float dt)
+{
+    if (!c || !f) return OCEAN_E_INVALID;
+    if (tile != OCEAN_ALL_TILES && tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!std::isfinite(f->threshold) || !std::isfinite(f->gain) || !std::isfinite(f->lifetime) || !std::isfinite(f->spread) || !std::isfinite(f->cutoff) ||
+        !std::isfinite(dt))
+        return OCEAN_E_INVALID;
+    if (!(f->lifetime > 0.0f) || f->spread < 0.0f || f->spread > 1.0f || f->cutoff < 0.0f || f->cutoff > 1.0f || dt < 0.0f) return OCEAN_E_INVALID;
+    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
+    const int set = c->last_set;
+    const int mode = c->set_mode[set];              // of the frame that wrote these maps, not of the next one
+    if (mode != OCEAN_MODE_FULL7 && mode != OCEAN_MODE_JACOBIAN) return OCEAN_E_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t first = tile == OCEAN_ALL_TILES ? 0u : tile, count = tile == OCEAN_ALL_TILES ? c->tiles : 1u;
+    const size_t n2 = (size_t)c->n * c->n;
+    FoamArgs a;
+    a.lambda = nullptr;
+    a.lambda_all = c->set_lambda[set][first];
+    if (mode == OCEAN_MODE_FULL7) {
+        bool uniform = true;
+        for (uint32_t i = first + 1; i < first + count && uniform; ++i) uniform = c->set_lambda[set][i] == a.lambda_all;
+        if (!uniform) {         // per-tile lambdas: the device copy is replaced only when they change, and then nothing in flight may still read it
+            if (c->foam_lambda_host != c->set_lambda[set]) {
+                SYNC_ALL(c);
+                if (!c->foam_lambda) HIP_TRY(hipMalloc(&c->foam_lambda, c->tiles * sizeof(float)));
+                HIP_TRY(hipMemcpy(c->foam_lambda, c->set_lambda[set].data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
+                c->foam_lambda_host = c->set_lambda[set];
+            }
+            a.lambda = c->foam_lambda + first;
+        }
+    }
+    hipStream_t st = stream_of(c, set);             // ordered after the frame that wrote these maps
+    CONSUMER_BEGIN(c, st);
+    { int rc_ = alloc_foam(c, st); if (rc_) return rc_; }
+    const float* src = c->foam[c->foam_cur];
+    float* dst = c->foam[c->foam_cur ^ 1];
+    const float4* maps = mode == OCEAN_MODE_JACOBIAN ? (c->ext_disp ? c->ext_disp : c->dispN[set]) : (c->ext_nrm ? c->ext_nrm : c->nrmN[set]);
+    a.map = maps + first * n2;
+    a.src = src + first * n2;
+    a.dst = dst + first * n2;
+    a.tile_texels = n2;
+    a.threshold = f->threshold; a.gain = f->gain; a.spread = f->spread; a.cutoff = f->cutoff;
+    a.decay = (float)std::exp(-(double)dt / (double)f->lifetime);
+    a.n = (int)c->n;
+    a.log2_groups = 0;
+    while ((4u << a.log2_groups) < c->n) ++a.log2_groups;
+    a.rows = (int)foam_band_rows(c, count);
+    const dim3 grid(foam_blocks(c->n, (unsigned)a.rows), count);
+    if (mode == OCEAN_MODE_JACOBIAN) hipLaunchKernelGGL(k_foam_update<FOAM_FROM_JACOBIAN>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_foam_update<FOAM_FROM_NORMALS>, grid, dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    // the tiles that were not selected keep their state in the buffer that is current from now on
+    if (first > 0) HIP_TRY(hipMemcpyAsync(dst, src, first * n2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (first + count < c->tiles)
+        HIP_TRY(hipMemcpyAsync(dst + (first + count) * n2, src + (first + count) * n2, (c->tiles - first - count) * n2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    CONSUMER_END(c, st);
+    c->foam_cur ^= 1;
+    c->foam_ready = true;
+    return OCEAN_OK;
+}
+
+int ocean_reset_foam(ocean_t* c)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (!c->foam[1]) return OCEAN_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, c->last_set);
+    CONSUMER_BEGIN(c, st);
+    HIP_TRY(hipMemsetAsync(c->foam[c->foam_cur], 0, (size_t)c->tiles * c->n * c->n * sizeof(float), st));
+    CONSUMER_END(c, st);
+    return OCEAN_OK;
+}
+
+int ocean_read_foam(ocean_t* c, uint32_t tile, float* out)
+{
+    if (!c || !out || tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!c->foam_ready) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    SYNC_ALL(c);
+    const size_t n2 = (size_t)c->n * c->n;
+    HIP_TRY(hipMemcpy(out, c->foam[c->foam_cur] + tile * n2, n2 * sizeof(float), hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+int ocean_device_foam(ocean_t* c, void** d_foam)
+{
+    if (!c || !d_foam) return OCEAN_E_INVALID;
+    *d_foam = c->foam_ready ? c->foam[c->foam_cur] : nullptr;
+    return OCEAN_OK;
+}
+
+}  // extern "C"
+
+// Checks and launch arguments shared by the two foam queries: the surface of the query, then the foam of its first tile.
+static int foam_query_args(ocean_ctx* c, const ocean_surface* s, FoamQueryArgs& a)
+{
+    { int rc_ = query_args(c, s, a.q); if (rc_) return rc_; }
+    if (!c->foam_ready) return OCEAN_E_NOT_READY;
+    a.foam = c->foam[c->foam_cur] + s->first_tile * a.q.tile_texels;
+    a.q.out_pos = nullptr; a.q.out_nrm = nullptr;
+    return OCEAN_OK;
+}
+
+static int launch_foam_query(ocean_ctx* c, const FoamQueryArgs& a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_query_foam, dim3((a.q.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_query_foam(ocean_t* c, const ocean_surface* s, const float* xz, uint32_t points, float* out)
+{
+    FoamQueryArgs a{};
+    { int rc_ = foam_query_args(c, s, a); if (rc_) return rc_; }
+    if (points == 0) return OCEAN_OK;
+    if (!xz || !out) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    if (points > c->foam_query_capacity) {
+        SYNC_ALL(c);
+        if (c->foam_query_buf) (void)hipFree(c->foam_query_buf);
+        c->foam_query_buf = nullptr; c->foam_query_capacity = 0;
+        HIP_TRY(hipMalloc(&c->foam_query_buf, (size_t)points * 6 * sizeof(float)));
+        c->foam_query_capacity = points;
+    }
+    // [results | points]: the float4 array first, so that both are aligned
+    float* d_out = c->foam_query_buf;
+    float* d_xz = d_out + (size_t)points * 4;
+    a.q.xz = reinterpret_cast<const float2*>(d_xz);
+    a.out = reinterpret_cast<float4*>(d_out);
+    a.q.points = points;
+    hipStream_t st = stream_of(c, c->last_set);             // ordered after the frame that wrote these maps and the foam's last update
+    CONSUMER_BEGIN(c, st);
+    HIP_TRY(hipMemcpyAsync(d_xz, xz, (size_t)points * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+    { int rc_ = launch_foam_query(c, a, st); if (rc_) return rc_; }
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)points * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    CONSUMER_END(c, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    return OCEAN_OK;
+}
+
+int ocean_query_foam_device(ocean_t* c, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out)
+{
+    FoamQueryArgs a{};
+    { int rc_ = foam_query_args(c, s, a); if (rc_) return rc_; }
+    if (points == 0) return OCEAN_OK;
+    if (!d_xz || !d_out) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    a.q.xz = static_cast<const float2*>(d_xz);
+    a.out = static_cast<float4*>(d_out);
+    a.q.points = points;
+    hipStream_t st = stream_of(c, c->last_set);
+    CONSUMER_BEGIN(c, st);
+    { int rc_ = launch_foam_query(c, a, st); if (rc_) return rc_; }
     CONSUMER_END(c, st);
     return OCEAN_OK;
 }

@@ -187,6 +187,14 @@ struct ocean_ctx {
     std::vector<float> set_length[MAXD];    //   (recorded when it is enqueued: what ocean_query_surface's Newton step needs)
     float* query_buf = nullptr;     // ocean_query_surface: staging of the points and results, 10 floats per point (grows on demand)
     uint32_t query_capacity = 0;    // points it holds
+    int set_mode[MAXD] = {};                //   ... and its OCEAN_MODE_*: which Jacobian ocean_update_foam finds in the maps
+    float* foam[2] = {};            // persistent foam (ocean_update_foam): two buffers [tiles][N][N] that alternate, allocated on first use
+    int foam_cur = 0;               // the one that holds the state after the most recently enqueued update
+    bool foam_ready = false;        // an update has been enqueued since the last ocean_prepare
+    float* foam_lambda = nullptr;   // [tiles] lambdas of a FULL7 frame whose tiles differ (uploaded when they change: foam_lambda_host)
+    std::vector<float> foam_lambda_host;
+    float* foam_query_buf = nullptr;    // ocean_query_foam: staging of the points and results, 6 floats per point (grows on demand)
+    uint32_t foam_query_capacity = 0;
     float* ray_buf = nullptr;       // ocean_raycast_surface: staging of the rays and results, 14 floats per ray (grows on demand)
     uint32_t ray_capacity = 0;      // rays it holds
     unsigned long long* stamps = nullptr;   // diagnostic builds only
