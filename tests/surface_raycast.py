@@ -1,5 +1,5 @@
 """float32 numpy restatement of the ray cast (include/ocean_consumers.h: ocean_raycast_surface; the kernel is k_raycast_surface in
-watersurfacerendering_amd/csrc/ocean_aux_kernels.h).  TEST INFRASTRUCTURE ONLY.
+watersurfacerendering_amd/csrc/ocean_consumer_kernels.h).  TEST INFRASTRUCTURE ONLY.
 
 The surface is the one of the surface query (tests/surface_query.py): H(x, z) is the height query_surface returns.  The rules of the
 header, in fp32 in the kernel's order: unit direction, gap f(t) = p(t).y - H(p(t).xz), the height slab |y| <= Hmax, a coarse march of

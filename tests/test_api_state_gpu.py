@@ -730,3 +730,61 @@ def test_compute_waves_read_refuses_a_partly_registered_destination():
     assert np.array_equal(a, a0) and np.array_equal(dd, d0) and np.array_equal(qq, q0)
     assert b.fault_recoveries == 0
     b.close()
+
+
+@pytest.mark.parametrize("depth", [1, 3])
+def test_host_blocking_consumers_share_one_staging_buffer(depth):
+    """ocean_query_surface, ocean_raycast_surface and ocean_query_foam stage their host arrays in ONE device buffer of the context
+    (ocean_ctx.h: staging).  A sequence that makes it grow, be reused at a smaller size by another kind of call, and grow again gives, call
+    for call, the 32-bit words of the same single call on a context driven alike that has made no other such call before it.
+    64^2, three tiles as three cascades, default mode; at depth 3 the frame the calls read is the third of three asynchronous ones (chain 2)."""
+    import watersurfacerendering_amd as W
+    lengths = [1000.0, 370.0, 130.0]
+    scales = [lengths[0] / L for L in lengths]
+    surface = dict(first_tile=0, uv_scales=scales, grid_size=512, vertex_distance=lengths[0] / 512)
+
+    def context():
+        b = W.OceanBatch(64, 3, 0)
+        for i, L in enumerate(lengths):
+            b.set_params(tile=i, tile_length=L)
+        b.set_pipeline_depth(depth)
+        b.prepare(SEED + 64)
+        for t in (1.3, 2.6, 3.9):
+            b.compute_waves_async(t)
+        b.update_foam(0.5, threshold=0.95)
+        return b
+
+    rng = np.random.default_rng(64 + depth)
+    def points(count):
+        return rng.uniform(-700.0, 700.0, (count, 2)).astype(np.float32)
+    def rays(count):        # from 5 .. 40 m above the rest level, mostly downwards
+        o = np.stack([rng.uniform(-600, 600, count), rng.uniform(5.0, 40.0, count), rng.uniform(-600, 600, count)], 1)
+        d = rng.normal(size=(count, 3))
+        d[:, 1] -= 0.6
+        return np.concatenate([o, d], axis=1).astype(np.float32)
+    query = lambda xz: lambda b: b.query_surface(xz, **surface)
+    cast = lambda r: lambda b: b.raycast_surface(r[:, :3], r[:, 3:], 1500.0, **surface)
+    foam = lambda xz: lambda b: (b.query_foam(xz, **surface),)
+    q257, r1000, f4099 = query(points(257)), cast(rays(1000)), foam(points(4099))
+    calls = [("query 257", q257), ("raycast 1000", r1000), ("foam 33", foam(points(33))), ("query 257 again", q257),
+             ("raycast 65", cast(rays(65))), ("foam 4099", f4099)]
+    words = lambda arrays: [np.ascontiguousarray(a).view(np.uint32) for a in arrays]
+
+    want = {}
+    for _, call in calls:
+        if call not in want:        # each on a context of its own, whose first host-blocking consumer call it is
+            r = context()
+            want[call] = words(call(r))
+            r.close()
+    # the inputs exercise something: rays that hit and rays that miss, foam present and absent
+    hits = int((want[r1000][0].view(np.float32)[:, 3] >= 0.0).sum())
+    foamy = int((want[f4099][0].view(np.float32)[:, 0] > 0.0).sum())
+    assert 50 < hits < 1000 and 40 < foamy < 4099, (hits, foamy)
+
+    b = context()
+    for name, call in calls:
+        got = words(call(b))
+        assert len(got) == len(want[call])
+        for k, (g, w) in enumerate(zip(got, want[call])):
+            assert np.array_equal(g, w), (depth, name, k, int((g != w).sum()))
+    b.close()

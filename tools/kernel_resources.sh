@@ -1,6 +1,7 @@
 #!/bin/bash
 # Registers, scratch, occupancy of every kernel of one translation unit (clang's kernel-resource-usage remarks).
 #   tools/kernel_resources.sh frames_2048 [pattern] [extra hipcc flags...]
+# Units: ocean_api (Prepare, pack), ocean_consumers (vertex stage, mips, query, ray cast, foam), frames_small / _mid / _2048 / _4096.
 cd "$(dirname "$0")/../watersurfacerendering_amd/csrc" || exit 1
 tu=${1:-frames_2048}; pat=${2:-k_}; shift 2
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function "$@" -S --cuda-device-only \

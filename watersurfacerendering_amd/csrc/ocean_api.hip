@@ -15,22 +15,11 @@
 #include <vector>
 
 #include "ocean_ctx.h"
-#include "ocean_aux_kernels.h"      // this translation unit also holds the Prepare(), read-out and consumer kernels
-#include "ocean_foam_kernels.h"     //   ... and the persistent foam's
+#include "ocean_aux_kernels.h"      // this translation unit also holds the Prepare() and pack kernels (the consumers': ocean_consumers.hip)
 
 using namespace ocean;
 
-static thread_local int g_last_hip = 0;
-
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t e_ = (expr);                         \
-        if (e_ != hipSuccess) {                         \
-            g_last_hip = (int)e_;                       \
-            (void)hipGetLastError();                    \
-            return e_ == hipErrorOutOfMemory ? OCEAN_E_NOMEM : OCEAN_E_HIP; \
-        }                                               \
-    } while (0)
+thread_local int ocean::g_last_hip = 0;     // the word HIP_TRY (ocean_ctx.h) leaves the runtime's error in, in both host units
 
 // Ranges page-locked through THIS library, with their device addresses (looked up once, at registration): ocean_compute_waves_read's copy
 // kernels store through them without asking the runtime on every call (hipHostGetDevicePointer costs a few microseconds of a 190 us call).
@@ -70,18 +59,10 @@ static void free_device(ocean_ctx* c)
     c->k1d = nullptr; c->tw = nullptr;
     c->toff = nullptr; c->lambda = nullptr; c->tparams = nullptr; c->xi = nullptr;
     c->h0h = nullptr; c->h0_inv_scale = nullptr; c->h0_maxbits = nullptr; c->zscale = nullptr; c->zbounds = nullptr;
-    if (c->query_buf) (void)hipFree(c->query_buf);
-    c->query_buf = nullptr; c->query_capacity = 0;
-    if (c->ray_buf) (void)hipFree(c->ray_buf);
-    c->ray_buf = nullptr; c->ray_capacity = 0;
-    for (float*& f : c->foam) { if (f) (void)hipFree(f); f = nullptr; }
-    if (c->foam_lambda) (void)hipFree(c->foam_lambda);
-    if (c->foam_query_buf) (void)hipFree(c->foam_query_buf);
-    c->foam_lambda = nullptr; c->foam_lambda_host.clear(); c->foam_query_buf = nullptr; c->foam_query_capacity = 0;
-    c->foam_cur = 0; c->foam_ready = false;
+    ocean_consumers_release(c, false);
     c->prepared = false; c->placement_done = false;
-    // nothing of the old buffers may be referred to any more: no frame, no chain to read out, no mips of the old size
-    c->have_frame = false; c->last_set = 0; c->frame_ctr = 0; c->mips_ready = false; c->grid_vertices = 0;
+    // nothing of the old buffers may be referred to any more: no frame, no chain to read out (no mips or grid of the old maps: above)
+    c->have_frame = false; c->last_set = 0; c->frame_ctr = 0;
     c->maps_shared = false;             // the exported / handed-out maps are gone with the buffers
 }
 
@@ -172,10 +153,7 @@ static int alloc_device(ocean_ctx* c)
     HIP_TRY(hipMalloc(&c->omega_q_overflow, sizeof(unsigned)));
     HIP_TRY(hipMalloc(&c->k1d, t * n * sizeof(float)));
     HIP_TRY(hipMalloc(&c->tw, n * sizeof(float2)));
-    {
-        int rc_ = alloc_set(c, 0);
-        if (rc_) return rc_;
-    }
+    OCEAN_TRY(alloc_set(c, 0));
     HIP_TRY(hipMalloc(&c->toff, t * sizeof(float)));
     HIP_TRY(hipMalloc(&c->lambda, t * sizeof(float)));
     HIP_TRY(hipMalloc(&c->tparams, t * sizeof(TileParams)));
@@ -218,7 +196,7 @@ static int drain_streams(ocean_ctx* c)
 static int recover_fault(ocean_ctx* c)
 {
     if (c->recovering) { g_last_hip = (int)hipErrorLaunchTimeOut; return OCEAN_E_HIP; }
-    { int rc_ = drain_streams(c); if (rc_) return rc_; }
+    OCEAN_TRY(drain_streams(c));
     bool consumed = c->consumer_pending;
     for (bool p : c->gather_pending) consumed = consumed || p;
     __atomic_store_n(c->fault, 0u, __ATOMIC_RELEASE);
@@ -238,16 +216,15 @@ static int recover_fault(ocean_ctx* c)
     if (fault_raised(c) || consumed) { g_last_hip = (int)hipErrorLaunchTimeOut; return OCEAN_E_HIP; }
     return OCEAN_OK;
 }
-static int check_fault(ocean_ctx* c) { return fault_raised(c) ? recover_fault(c) : OCEAN_OK; }
+int check_fault(ocean_ctx* c) { return fault_raised(c) ? recover_fault(c) : OCEAN_OK; }
 
-static int sync_all(ocean_ctx* c)
+int sync_all(ocean_ctx* c)
 {
-    { int rc_ = drain_streams(c); if (rc_) return rc_; }
+    OCEAN_TRY(drain_streams(c));
     if (fault_raised(c)) return recover_fault(c);   // (resets the pipeline bookkeeping whatever it returns)
     reset_pipeline_state(c);
     return OCEAN_OK;
 }
-#define SYNC_ALL(c) do { int rc_ = sync_all(c); if (rc_) return rc_; } while (0)
 
 extern "C" {
 
@@ -339,11 +316,7 @@ void ocean_destroy(ocean_t* c)
     free_device(c);
     if (c->h_minmax) (void)hipHostFree(c->h_minmax);
     if (c->fault) (void)hipHostFree(c->fault);
-    if (c->grid_pos) (void)hipFree(c->grid_pos);
-    if (c->mips_disp) (void)hipFree(c->mips_disp);
-    if (c->mips_nrm) (void)hipFree(c->mips_nrm);
-    if (c->grid_nrm) (void)hipFree(c->grid_nrm);
-    if (c->consumer_ev) (void)hipEventDestroy(c->consumer_ev);
+    ocean_consumers_release(c, true);
     if (c->start_ev) (void)hipEventDestroy(c->start_ev);
     for (auto& e : c->end_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->z_done) if (e) (void)hipEventDestroy(e);
@@ -399,7 +372,7 @@ int ocean_set_tile_size(ocean_t* c, uint32_t tile_size)
     if (!size_ok(tile_size)) return OCEAN_E_UNSUPPORTED;
     if (tile_size == c->n) return OCEAN_OK;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     free_device(c);
     c->n = tile_size;
     release_import(c);
@@ -445,7 +418,7 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
         tp[i].dispersion_param = c->dispersion_param;
         tp[i].seed = seed + i;
     }
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     HIP_TRY(hipMemcpy(c->tparams, tp.data(), t * sizeof(TileParams), hipMemcpyHostToDevice));
     if (!c->xi) HIP_TRY(hipMalloc(&c->xi, t * n2 * sizeof(float2)));
     if (xi_or_null) HIP_TRY(hipMemcpy(c->xi, xi_or_null, t * n2 * sizeof(float2), hipMemcpyHostToDevice));
@@ -476,7 +449,7 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
         // the two precisions lay the same elements out at 8 or 4 bytes each: what one wrote sits in the other's
         // padding columns, which must read as zero -> zero-fill every allocated chain again
         const size_t nu = n / 2 + 1, nup = (n / 2 + 16) & ~(size_t)15;
-        SYNC_ALL(c);
+        OCEAN_TRY(sync_all(c));
         for (int i = 0; i < MAXD; ++i)
             if (c->z[i]) {
                 HIP_TRY(hipMemsetAsync(c->z[i], 0, t * 3 * nu * 2 * nup * sizeof(float2), stream_of(c, i)));
@@ -525,7 +498,7 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
         for (float* f : c->foam) HIP_TRY(hipMemsetAsync(f, 0, foam_bytes, stream_of(c, 0)));
     }
     c->foam_ready = false;
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     {
         unsigned overflow = 1;
         HIP_TRY(hipMemcpy(&overflow, c->omega_q_overflow, sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -569,24 +542,15 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     // pass of one frame fills the memory-idle phases of the others' map passes.
     // Caller-bound output buffers or a caller stream force depth 1.
     const bool pipe = pipelined && c->depth > 1 && !c->user && !c->ext_disp && !c->ext_nrm;
-    if (!pipe && c->depth > 1 && pipelined && !redo) {  // leaving pipelined mode: drain the other chains first
-        int rc_ = sync_all(c);
-        if (rc_) return rc_;
-    }
+    if (!pipe && c->depth > 1 && pipelined && !redo) OCEAN_TRY(sync_all(c));    // leaving pipelined mode: drain the other chains first
     const int set = redo ? redo_set : (pipe ? (int)(c->frame_ctr % (uint64_t)c->depth) : 0);
-    {
-        int rc_ = alloc_set(c, set);
-        if (rc_) return rc_;
-    }
+    OCEAN_TRY(alloc_set(c, set));
     hipStream_t st = stream_of(c, set);
     if (c->gather_pending[set]) {        // this chain's maps are still being sent: the frame may not rewrite them yet
         HIP_TRY(hipStreamWaitEvent(st, c->gather_done[set], 0));
         c->gather_pending[set] = false;
     }
-    if (c->mode == OCEAN_MODE_JACOBIAN) {
-        int rc_ = alloc_jacobian(c, set);
-        if (rc_) return rc_;
-    }
+    if (c->mode == OCEAN_MODE_JACOBIAN) OCEAN_TRY(alloc_jacobian(c, set));
     FrameArgs a;
     a.h0 = c->h0; a.omega = c->omega; a.k1d = c->k1d; a.tw = c->tw;
     a.omega_q = c->omega16 ? c->omega_q : nullptr; a.base_freq = c->base_freq;
@@ -604,8 +568,8 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     c->seq[set] = frame_seq;
     c->frame_valid[set] = false;
     a.frame_seq = frame_seq;
-    a.disp = c->ext_disp ? c->ext_disp : c->dispN[set];
-    a.nrm = c->ext_nrm ? c->ext_nrm : c->nrmN[set];
+    a.disp = maps_of(c, set).disp;
+    a.nrm = maps_of(c, set).nrm;
     a.toff = c->use_toff ? c->toff : nullptr;
     {   // choppiness: by value when all tiles agree, else the per-tile device array (uploaded when it changed)
         if (c->lambda_dirty) {
@@ -616,8 +580,7 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
         a.lambda_all = c->params[0].lambda;
         a.lambda = uniform ? nullptr : c->lambda;
         if (!uniform && c->lambda_dirty) {
-            int rc_ = sync_all(c);                      // frames in flight still read the old array
-            if (rc_) return rc_;
+            OCEAN_TRY(sync_all(c));                      // frames in flight still read the old array
             std::vector<float> l(c->tiles);
             for (uint32_t i = 0; i < c->tiles; ++i) l[i] = c->params[i].lambda;
             HIP_TRY(hipMemcpy(c->lambda, l.data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
@@ -741,7 +704,7 @@ static int placement_search(ocean_ctx* c)
     if (trials <= 1 || !mask) { c->placement_done = true; return OCEAN_OK; }
     if (c->user || c->ext_disp || c->ext_nrm || c->h0_bits == 16) return OCEAN_OK;          // (not now: a later Prepare may)
     c->placement_done = true;
-    { int rc_ = alloc_set(c, 0); if (rc_) return rc_; }
+    OCEAN_TRY(alloc_set(c, 0));
     hipStream_t st = stream_of(c, 0);
     struct Group { void* p[NB]; };
     std::vector<Group> cand((size_t)trials);
@@ -846,7 +809,7 @@ int ocean_synchronize(ocean_t* c)
 {
     if (!c) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     return OCEAN_OK;
 }
 
@@ -892,7 +855,7 @@ static int wait_frame(ocean_ctx* c, int set)
     if (!fault_raised(c) || attempt > 0) break;
     // an in-launch wait of some frame of this context gave up: recover (this chain's frame is run again if it was one of them -- new
     // sequence number, everything drained) and read the records once more
-    { int rc_ = recover_fault(c); if (rc_) return rc_; }
+    OCEAN_TRY(recover_fault(c));
     if (!c->frame_valid[set]) return OCEAN_E_NOT_READY;
     }
     return fault_raised(c) ? OCEAN_E_HIP : OCEAN_OK;
@@ -931,7 +894,7 @@ int ocean_set_time_offsets(ocean_t* c, const float* offsets)
 {
     if (!c) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     if (!offsets) { c->use_toff = false; c->toff_host.clear(); return OCEAN_OK; }
     c->toff_host.assign(offsets, offsets + c->tiles);
     HIP_TRY(hipMemcpy(c->toff, c->toff_host.data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
@@ -958,9 +921,9 @@ int ocean_read_maps(ocean_t* c, uint32_t first, uint32_t count, float* disp, flo
     if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
-    const float4* d = (c->ext_disp ? c->ext_disp : c->dispN[c->last_set]) + first * n2;
-    const float4* q = (c->ext_nrm ? c->ext_nrm : c->nrmN[c->last_set]) + first * n2;
-    SYNC_ALL(c);
+    const float4* d = maps_of(c, c->last_set).disp + first * n2;
+    const float4* q = maps_of(c, c->last_set).nrm + first * n2;
+    OCEAN_TRY(sync_all(c));
     if (disp) HIP_TRY(hipMemcpy(disp, d, count * n2 * sizeof(float4), hipMemcpyDeviceToHost));
     if (nrm) HIP_TRY(hipMemcpy(nrm, q, count * n2 * sizeof(float4), hipMemcpyDeviceToHost));
     return OCEAN_OK;
@@ -994,8 +957,8 @@ int ocean_compute_waves_read(ocean_t* c, float t, float* out_amp, float* disp, f
     if (rc) return rc;
     const int set = c->last_set;
     hipStream_t st = stream_of(c, set);
-    const float4* d = c->ext_disp ? c->ext_disp : c->dispN[set];
-    const float4* q = c->ext_nrm ? c->ext_nrm : c->nrmN[set];
+    const float4* d = maps_of(c, set).disp;
+    const float4* q = maps_of(c, set).nrm;
     hipStream_t nst = st;
     if (!direct) {
         if (c->after_b_recorded) {      // (frames whose x axis is one launch -- small tiles -- have no such point: both copies follow the frame)
@@ -1076,8 +1039,8 @@ int ocean_read_maps_async(ocean_t* c, uint32_t first, uint32_t count, float* dis
     if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
-    const float4* d = (c->ext_disp ? c->ext_disp : c->dispN[c->last_set]) + first * n2;
-    const float4* q = (c->ext_nrm ? c->ext_nrm : c->nrmN[c->last_set]) + first * n2;
+    const float4* d = maps_of(c, c->last_set).disp + first * n2;
+    const float4* q = maps_of(c, c->last_set).nrm + first * n2;
     hipStream_t st = stream_of(c, c->last_set);          // ordered after the frame that wrote these maps
     if (disp) HIP_TRY(hipMemcpyAsync(disp, d, count * n2 * sizeof(float4), hipMemcpyDeviceToHost, st));
     if (nrm) HIP_TRY(hipMemcpyAsync(nrm, q, count * n2 * sizeof(float4), hipMemcpyDeviceToHost, st));
@@ -1098,8 +1061,8 @@ int ocean_read_maps_staging(ocean_t* c, uint32_t tile, void* mapped_base, size_t
     HIP_TRY(hipSetDevice(c->device));
     const size_t map_bytes = (size_t)c->n * c->n * sizeof(float4);
     const size_t off = ocean_staging_map_offset(vertices_bytes, indices_bytes);
-    const float4* d = (c->ext_disp ? c->ext_disp : c->dispN[c->last_set]) + (size_t)tile * c->n * c->n;
-    const float4* q = (c->ext_nrm ? c->ext_nrm : c->nrmN[c->last_set]) + (size_t)tile * c->n * c->n;
+    const float4* d = maps_of(c, c->last_set).disp + (size_t)tile * c->n * c->n;
+    const float4* q = maps_of(c, c->last_set).nrm + (size_t)tile * c->n * c->n;
     hipStream_t st = stream_of(c, c->last_set);           // ordered behind the frame that wrote these maps
     char* base = static_cast<char*>(mapped_base);
     // [vertices | indices | pad to 16 | displacements | normals]  (WaterSurfaceMesh.cpp:712-744)
@@ -1112,8 +1075,8 @@ int ocean_read_maps_staging(ocean_t* c, uint32_t tile, void* mapped_base, size_t
 int ocean_device_maps(ocean_t* c, void** d_disp, void** d_nrm)
 {
     if (!c) return OCEAN_E_INVALID;
-    if (d_disp) *d_disp = c->ext_disp ? (void*)c->ext_disp : (void*)c->dispN[c->last_set];
-    if (d_nrm) *d_nrm = c->ext_nrm ? (void*)c->ext_nrm : (void*)c->nrmN[c->last_set];
+    if (d_disp) *d_disp = maps_of(c, c->last_set).disp;
+    if (d_nrm) *d_nrm = maps_of(c, c->last_set).nrm;
     c->maps_shared = true;              // somebody outside the context's streams may read the maps from now on: see wait_frame
     return OCEAN_OK;
 }
@@ -1132,10 +1095,7 @@ int ocean_export_maps(ocean_t* c, int* dmabuf_fd, size_t* disp_offset, size_t* n
     if (c->ext_disp || c->ext_nrm) return OCEAN_E_UNSUPPORTED;          // caller-bound output: the caller owns (and exports) that memory
     HIP_TRY(hipSetDevice(c->device));
     const int set = c->have_frame ? c->last_set : 0;
-    {
-        int rc_ = alloc_set(c, set);
-        if (rc_) return rc_;
-    }
+    OCEAN_TRY(alloc_set(c, set));
     int fd = -1;
     HIP_TRY(hipMemGetHandleForAddressRange(&fd, (hipDeviceptr_t)c->dispN[set], c->maps_bytes[set], hipMemRangeHandleTypeDmaBufFd, 0));
     *dmabuf_fd = fd;
@@ -1157,7 +1117,7 @@ int ocean_bind_output(ocean_t* c, void* d_disp, void* d_nrm)
     if (!c) return OCEAN_E_INVALID;
     if (((uintptr_t)d_disp | (uintptr_t)d_nrm) & 15u) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     release_import(c);                  // a binding made by ocean_bind_output_dmabuf ends here
     c->ext_disp = (float4*)d_disp;
     c->ext_nrm = (float4*)d_nrm;
@@ -1172,7 +1132,7 @@ int ocean_bind_output_dmabuf(ocean_t* c, int dmabuf_fd, size_t bytes, size_t dis
     if (map_bytes > bytes || disp_offset > bytes - map_bytes || nrm_offset > bytes - map_bytes) return OCEAN_E_INVALID;     // (no sum that could wrap)
     if (disp_offset < nrm_offset + map_bytes && nrm_offset < disp_offset + map_bytes) return OCEAN_E_INVALID;      // the two maps overlap
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     hipExternalMemoryHandleDesc hd = {};
     hd.type = hipExternalMemoryHandleTypeOpaqueFd;        // what amdgpu's dma-buf descriptors are imported as
     hd.handle.fd = dmabuf_fd;
@@ -1191,554 +1151,13 @@ int ocean_bind_output_dmabuf(ocean_t* c, int dmabuf_fd, size_t bytes, size_t dis
     return OCEAN_OK;
 }
 
-}  // extern "C"
-
-// The consumer kernels (vertex stage, mip chain) write context-wide output buffers and run on the stream of the frame they read.
-// At pipeline depth > 1 consecutive consumer calls land on different, mutually unordered chain streams: each call first makes
-// its stream wait for the previous consumer launch, so that two of them never write those buffers at once.
-static int consumer_begin(ocean_ctx* c, hipStream_t st)
-{
-    // (a frame whose in-launch wait has given up by now is recovered before anything consumes it; one that gives up later is reported
-    //  by the next wait / synchronisation: recover_fault)
-    { int rc_ = check_fault(c); if (rc_) return rc_; }
-    if (c->consumer_pending && c->consumer_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->consumer_ev, 0));
-    return OCEAN_OK;
-}
-static int consumer_end(ocean_ctx* c, hipStream_t st)
-{
-    if (!c->consumer_ev) HIP_TRY(hipEventCreateWithFlags(&c->consumer_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->consumer_ev, st));
-    c->consumer_stream = st;
-    c->consumer_pending = true;
-    return OCEAN_OK;
-}
-#define CONSUMER_BEGIN(c, st) do { int rc_ = consumer_begin(c, st); if (rc_) return rc_; } while (0)
-#define CONSUMER_END(c, st) do { int rc_ = consumer_end(c, st); if (rc_) return rc_; } while (0)
-
-extern "C" {
-
-int ocean_displace_grid(ocean_t* c, uint32_t tile, uint32_t grid_size, float vertex_distance, float uv_scale, float choppy)
-{
-    if (!c || tile >= c->tiles || grid_size == 0 || grid_size > 8192) return OCEAN_E_INVALID;
-    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    const uint32_t verts = (grid_size + 1) * (grid_size + 1);
-    if (verts > c->grid_capacity) {
-        SYNC_ALL(c);
-        if (c->grid_pos) (void)hipFree(c->grid_pos);
-        if (c->grid_nrm) (void)hipFree(c->grid_nrm);
-        c->grid_pos = c->grid_nrm = nullptr; c->grid_capacity = 0;
-        HIP_TRY(hipMalloc(&c->grid_pos, (size_t)verts * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c->grid_nrm, (size_t)verts * sizeof(float4)));
-        c->grid_capacity = verts;
-    }
-    const size_t n2 = (size_t)c->n * c->n;
-    GridArgs g;
-    g.disp = (c->ext_disp ? c->ext_disp : c->dispN[c->last_set]) + tile * n2;
-    g.nrm = (c->ext_nrm ? c->ext_nrm : c->nrmN[c->last_set]) + tile * n2;
-    g.minmax = c->minmax[c->last_set] + 2 * tile;
-    g.positions = c->grid_pos; g.normals = c->grid_nrm;
-    g.n = (int)c->n; g.grid = (int)grid_size;
-    g.vertex_distance = vertex_distance; g.uv_scale = uv_scale; g.choppy = choppy;
-    // ordered after the frame that wrote these maps
-    CONSUMER_BEGIN(c, stream_of(c, c->last_set));
-    hipLaunchKernelGGL(k_displace_grid, dim3((verts + 255) / 256), dim3(256), 0, stream_of(c, c->last_set), g);
-    HIP_TRY(hipGetLastError());
-    CONSUMER_END(c, stream_of(c, c->last_set));
-    c->grid_vertices = verts;
-    return OCEAN_OK;
-}
-
-int ocean_displace_grid_cascades(ocean_t* c, uint32_t first_tile, uint32_t count, uint32_t grid_size, float vertex_distance,
-                                 const float* uv_scales, float choppy)
-{
-    if (!c || !uv_scales || count == 0 || count > (uint32_t)OCEAN_MAX_CASCADES || first_tile >= c->tiles || first_tile + count > c->tiles ||
-        grid_size == 0 || grid_size > 8192)
-        return OCEAN_E_INVALID;
-    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    const uint32_t verts = (grid_size + 1) * (grid_size + 1);
-    if (verts > c->grid_capacity) {
-        SYNC_ALL(c);
-        if (c->grid_pos) (void)hipFree(c->grid_pos);
-        if (c->grid_nrm) (void)hipFree(c->grid_nrm);
-        c->grid_pos = c->grid_nrm = nullptr; c->grid_capacity = 0;
-        HIP_TRY(hipMalloc(&c->grid_pos, (size_t)verts * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c->grid_nrm, (size_t)verts * sizeof(float4)));
-        c->grid_capacity = verts;
-    }
-    const size_t n2 = (size_t)c->n * c->n;
-    CascadeArgs a;
-    a.g.disp = (c->ext_disp ? c->ext_disp : c->dispN[c->last_set]) + first_tile * n2;
-    a.g.nrm = (c->ext_nrm ? c->ext_nrm : c->nrmN[c->last_set]) + first_tile * n2;
-    a.g.minmax = c->minmax[c->last_set] + 2 * first_tile;
-    a.g.positions = c->grid_pos; a.g.normals = c->grid_nrm;
-    a.g.n = (int)c->n; a.g.grid = (int)grid_size;
-    a.g.vertex_distance = vertex_distance; a.g.uv_scale = 1.0f; a.g.choppy = choppy;
-    a.count = (int)count; a.tile_texels = n2;
-    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) a.uv_scale[i] = i < count ? uv_scales[i] : 0.0f;
-    CONSUMER_BEGIN(c, stream_of(c, c->last_set));
-    hipLaunchKernelGGL(k_displace_grid_cascades, dim3((verts + 255) / 256), dim3(256), 0, stream_of(c, c->last_set), a);
-    HIP_TRY(hipGetLastError());
-    CONSUMER_END(c, stream_of(c, c->last_set));
-    c->grid_vertices = verts;
-    return OCEAN_OK;
-}
-
-int ocean_read_grid(ocean_t* c, float* positions, float* normals)
-{
-    if (!c) return OCEAN_E_INVALID;
-    if (!c->grid_vertices) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
-    if (positions) HIP_TRY(hipMemcpy(positions, c->grid_pos, (size_t)c->grid_vertices * sizeof(float4), hipMemcpyDeviceToHost));
-    if (normals) HIP_TRY(hipMemcpy(normals, c->grid_nrm, (size_t)c->grid_vertices * sizeof(float4), hipMemcpyDeviceToHost));
-    return OCEAN_OK;
-}
-
-int ocean_device_grid(ocean_t* c, void** d_positions, void** d_normals, uint32_t* vertices)
-{
-    if (!c) return OCEAN_E_INVALID;
-    if (d_positions) *d_positions = c->grid_pos;
-    if (d_normals) *d_normals = c->grid_nrm;
-    if (vertices) *vertices = c->grid_vertices;
-    return OCEAN_OK;
-}
-
-size_t ocean_mip_texels(uint32_t n) { return ((size_t)n * n - 1) / 3; }      // sum of (n >> l)^2, l = 1 .. log2 n
-
-int ocean_build_mips(ocean_t* c, uint32_t tile)
-{
-    if (!c || tile >= c->tiles) return OCEAN_E_INVALID;
-    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    const uint32_t n = c->n;
-    if (c->mips_n != n) {
-        SYNC_ALL(c);
-        if (c->mips_disp) (void)hipFree(c->mips_disp);
-        if (c->mips_nrm) (void)hipFree(c->mips_nrm);
-        c->mips_disp = c->mips_nrm = nullptr; c->mips_n = 0; c->mips_ready = false;
-        HIP_TRY(hipMalloc(&c->mips_disp, ocean_mip_texels(n) * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c->mips_nrm, ocean_mip_texels(n) * sizeof(float4)));
-        c->mips_n = n;
-    }
-    const size_t n2 = (size_t)n * n;
-    MipArgs m;
-    m.src[0] = (c->ext_disp ? c->ext_disp : c->dispN[c->last_set]) + tile * n2;
-    m.src[1] = (c->ext_nrm ? c->ext_nrm : c->nrmN[c->last_set]) + tile * n2;
-    m.dst[0] = c->mips_disp; m.dst[1] = c->mips_nrm;
-    hipStream_t st = stream_of(c, c->last_set);            // ordered after the frame that wrote these maps
-    CONSUMER_BEGIN(c, st);
-    for (uint32_t w = n / 2; w >= 1; w /= 2) {
-        m.w = (int)w;
-        hipLaunchKernelGGL(k_mip_level, dim3((w * w + 255) / 256, 2), dim3(256), 0, st, m);
-        m.src[0] = m.dst[0]; m.src[1] = m.dst[1];
-        m.dst[0] += (size_t)w * w; m.dst[1] += (size_t)w * w;
-    }
-    HIP_TRY(hipGetLastError());
-    CONSUMER_END(c, st);
-    c->mips_ready = true;
-    return OCEAN_OK;
-}
-
-int ocean_read_mips(ocean_t* c, float* disp_mips, float* nrm_mips)
-{
-    if (!c) return OCEAN_E_INVALID;
-    if (!c->mips_ready) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
-    const size_t bytes = ocean_mip_texels(c->mips_n) * sizeof(float4);
-    if (disp_mips) HIP_TRY(hipMemcpy(disp_mips, c->mips_disp, bytes, hipMemcpyDeviceToHost));
-    if (nrm_mips) HIP_TRY(hipMemcpy(nrm_mips, c->mips_nrm, bytes, hipMemcpyDeviceToHost));
-    return OCEAN_OK;
-}
-
-int ocean_device_mips(ocean_t* c, void** d_disp_mips, void** d_nrm_mips, uint32_t* levels)
-{
-    if (!c) return OCEAN_E_INVALID;
-    if (d_disp_mips) *d_disp_mips = c->mips_ready ? c->mips_disp : nullptr;
-    if (d_nrm_mips) *d_nrm_mips = c->mips_ready ? c->mips_nrm : nullptr;
-    if (levels) { uint32_t l = 0; for (uint32_t w = c->mips_n; c->mips_ready && w > 1; w /= 2) ++l; *levels = l; }
-    return OCEAN_OK;
-}
-
-}  // extern "C"
-
-// Checks and launch arguments shared by the two surface queries (the device pointers are filled in by the caller).
-static int query_args(ocean_ctx* c, const ocean_surface* s, QueryArgs& a)
-{
-    if (!c || !s || s->cascades == 0 || s->cascades > (uint32_t)OCEAN_MAX_CASCADES || s->first_tile >= c->tiles ||
-        s->cascades > c->tiles - s->first_tile || s->grid_size == 0 || s->iterations > 32)
-        return OCEAN_E_INVALID;
-    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
-    const int set = c->last_set;
-    const size_t n2 = (size_t)c->n * c->n;
-    a.disp = (c->ext_disp ? c->ext_disp : c->dispN[set]) + s->first_tile * n2;
-    a.nrm = (c->ext_nrm ? c->ext_nrm : c->nrmN[set]) + s->first_tile * n2;
-    a.minmax = c->minmax[set] + 2 * s->first_tile;
-    a.tile_texels = n2;
-    a.n = (int)c->n;
-    a.count = (int)s->cascades;
-    a.iterations = s->iterations ? (int)s->iterations : 8;
-    a.grid = (float)s->grid_size;
-    a.half = (float)(s->grid_size / 2);
-    a.vertex_distance = s->vertex_distance;
-    a.choppy = s->choppy;
-    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) {
-        a.uv_scale[i] = i < s->cascades ? s->uv_scales[i] : 0.0f;
-        a.gain[i] = 0.0f;
-        if (i < s->cascades) {      // lambda_c * (s_c * L_c / (grid * vertex_distance)) of the frame that wrote tile c's maps
-            const uint32_t tile = s->first_tile + i;
-            a.gain[i] = c->set_lambda[set][tile] * (s->uv_scales[i] * c->set_length[set][tile] / (a.grid * s->vertex_distance));
-        }
-    }
-    return OCEAN_OK;
-}
-
-static int launch_query(ocean_ctx* c, const QueryArgs& a, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_query_surface, dim3((a.points + 255u) / 256u), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return OCEAN_OK;
-}
-
-extern "C" {
-
-int ocean_query_surface(ocean_t* c, const ocean_surface* s, const float* xz, uint32_t points, float* out_pos, float* out_nrm)
-{
-    QueryArgs a;
-    { int rc_ = query_args(c, s, a); if (rc_) return rc_; }
-    if (points == 0) return OCEAN_OK;
-    if (!xz || !out_pos || !out_nrm) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    if (points > c->query_capacity) {
-        SYNC_ALL(c);
-        if (c->query_buf) (void)hipFree(c->query_buf);
-        c->query_buf = nullptr; c->query_capacity = 0;
-        HIP_TRY(hipMalloc(&c->query_buf, (size_t)points * 10 * sizeof(float)));
-        c->query_capacity = points;
-    }
-    // [positions | normals | points]: the float4 arrays first, so that every array is 16-byte aligned
-    float* d_pos = c->query_buf;
-    float* d_nrm = d_pos + (size_t)points * 4;
-    float* d_xz = d_nrm + (size_t)points * 4;
-    a.xz = reinterpret_cast<const float2*>(d_xz);
-    a.out_pos = reinterpret_cast<float4*>(d_pos);
-    a.out_nrm = reinterpret_cast<float4*>(d_nrm);
-    a.points = points;
-    hipStream_t st = stream_of(c, c->last_set);             // ordered after the frame that wrote these maps
-    CONSUMER_BEGIN(c, st);
-    HIP_TRY(hipMemcpyAsync(d_xz, xz, (size_t)points * 2 * sizeof(float), hipMemcpyHostToDevice, st));
-    { int rc_ = launch_query(c, a, st); if (rc_) return rc_; }
-    HIP_TRY(hipMemcpyAsync(out_pos, d_pos, (size_t)points * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_nrm, d_nrm, (size_t)points * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-    CONSUMER_END(c, st);
-    HIP_TRY(hipStreamSynchronize(st));
-    return OCEAN_OK;
-}
-
-int ocean_query_surface_device(ocean_t* c, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out_pos, void* d_out_nrm)
-{
-    QueryArgs a;
-    { int rc_ = query_args(c, s, a); if (rc_) return rc_; }
-    if (points == 0) return OCEAN_OK;
-    if (!d_xz || !d_out_pos || !d_out_nrm) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    a.xz = static_cast<const float2*>(d_xz);
-    a.out_pos = static_cast<float4*>(d_out_pos);
-    a.out_nrm = static_cast<float4*>(d_out_nrm);
-    a.points = points;
-    hipStream_t st = stream_of(c, c->last_set);
-    CONSUMER_BEGIN(c, st);
-    { int rc_ = launch_query(c, a, st); if (rc_) return rc_; }
-    CONSUMER_END(c, st);
-    return OCEAN_OK;
-}
-
-}  // extern "C"
-
-// Checks and launch arguments shared by the two ray casts: the surface of the query, then the ray settings.
-static int raycast_args(ocean_ctx* c, const ocean_surface* s, const ocean_raycast* r, RaycastArgs& a)
-{
-    if (!c || !s || !r || !(r->max_distance > 0.0f) || !std::isfinite(r->max_distance) || r->steps > 4096 || r->refine > 8)
-        return OCEAN_E_INVALID;
-    { int rc_ = query_args(c, s, a.q); if (rc_) return rc_; }
-    a.max_distance = r->max_distance;
-    a.steps = r->steps ? (int)r->steps : 64;
-    a.refine = r->refine ? (int)r->refine : 3;
-    return OCEAN_OK;
-}
-
-static int launch_raycast(ocean_ctx* c, const RaycastArgs& a, hipStream_t st)
-{
-    const unsigned rays_per_block = 256u / RAYCAST_LANES;
-    hipLaunchKernelGGL(k_raycast_surface, dim3((unsigned)(((uint64_t)a.count + rays_per_block - 1u) / rays_per_block)), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return OCEAN_OK;
-}
-
-extern "C" {
-
-int ocean_raycast_surface(ocean_t* c, const ocean_surface* s, const ocean_raycast* r, const float* rays, uint32_t count,
-                          float* out_hit, float* out_nrm)
-{
-    RaycastArgs a{};
-    { int rc_ = raycast_args(c, s, r, a); if (rc_) return rc_; }
-    if (count == 0) return OCEAN_OK;
-    if (!rays || !out_hit || !out_nrm) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    if (count > c->ray_capacity) {
-        SYNC_ALL(c);
-        if (c->ray_buf) (void)hipFree(c->ray_buf);
-        c->ray_buf = nullptr; c->ray_capacity = 0;
-        HIP_TRY(hipMalloc(&c->ray_buf, (size_t)count * 14 * sizeof(float)));
-        c->ray_capacity = count;
-    }
-    // [hits | normals | rays]: the float4 arrays first, so that every array is 16-byte aligned
-    float* d_hit = c->ray_buf;
-    float* d_nrm = d_hit + (size_t)count * 4;
-    float* d_rays = d_nrm + (size_t)count * 4;
-    a.rays = d_rays;
-    a.out_hit = reinterpret_cast<float4*>(d_hit);
-    a.out_nrm = reinterpret_cast<float4*>(d_nrm);
-    a.count = count;
-    hipStream_t st = stream_of(c, c->last_set);             // ordered after the frame that wrote these maps
-    CONSUMER_BEGIN(c, st);
-    HIP_TRY(hipMemcpyAsync(d_rays, rays, (size_t)count * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-    { int rc_ = launch_raycast(c, a, st); if (rc_) return rc_; }
-    HIP_TRY(hipMemcpyAsync(out_hit, d_hit, (size_t)count * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_nrm, d_nrm, (size_t)count * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-    CONSUMER_END(c, st);
-    HIP_TRY(hipStreamSynchronize(st));
-    return OCEAN_OK;
-}
-
-int ocean_raycast_surface_device(ocean_t* c, const ocean_surface* s, const ocean_raycast* r, const void* d_rays, uint32_t count,
-                                 void* d_out_hit, void* d_out_nrm)
-{
-    RaycastArgs a{};
-    { int rc_ = raycast_args(c, s, r, a); if (rc_) return rc_; }
-    if (count == 0) return OCEAN_OK;
-    if (!d_rays || !d_out_hit || !d_out_nrm) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    a.rays = static_cast<const float*>(d_rays);
-    a.out_hit = static_cast<float4*>(d_out_hit);
-    a.out_nrm = static_cast<float4*>(d_out_nrm);
-    a.count = count;
-    hipStream_t st = stream_of(c, c->last_set);
-    CONSUMER_BEGIN(c, st);
-    { int rc_ = launch_raycast(c, a, st); if (rc_) return rc_; }
-    CONSUMER_END(c, st);
-    return OCEAN_OK;
-}
-
-}  // extern "C"
-
-// ---- persistent foam (include/ocean_consumers.h) -----------------------------------------------------------------------------------------
-// Both buffers or none (as alloc_jacobian): zero-filled on the stream of the update that asked for them.
-static int alloc_foam(ocean_ctx* c, hipStream_t st)
-{
-    if (c->foam[1]) return OCEAN_OK;               // the second of the two: complete
-    const size_t bytes = (size_t)c->tiles * c->n * c->n * sizeof(float);
-    for (int k = 0; k < 2; ++k) {
-        if (c->foam[k]) { (void)hipFree(c->foam[k]); c->foam[k] = nullptr; }       // leftovers of an earlier failed attempt
-        if (hipMalloc(&c->foam[k], bytes) != hipSuccess || hipMemsetAsync(c->foam[k], 0, bytes, st) != hipSuccess) {
-            for (int j = 0; j <= k; ++j) if (c->foam[j]) { (void)hipFree(c->foam[j]); c->foam[j] = nullptr; }
-            g_last_hip = (int)hipGetLastError();
-            return OCEAN_E_NOMEM;
-        }
-    }
-    c->foam_cur = 0; c->foam_ready = false;
-    return OCEAN_OK;
-}
-
-// Rows per band of k_foam_update's row walk: as long as the launch still has four waves for every compute unit (a band re-reads two rows of F).
-static unsigned foam_band_rows(const ocean_ctx* c, uint32_t tiles)
-{
-    const double waves_per_row = (double)tiles * c->n * c->n / 256.0;
-    unsigned rows = 32;
-    while (rows > 4 && waves_per_row / rows < 4.0 * (c->cu_count > 0 ? c->cu_count : 256)) rows /= 2;
-    return rows < c->n ? rows : c->n;
-}
-
-extern "C" {
-
-void ocean_default_foam(ocean_foam* f)
-{
-    if (!f) return;
-    f->threshold = 0.6f;
-    f->gain = 2.5f;
-    f->lifetime = 4.0f;
-    f->spread = 0.25f;
-    f->cutoff = 1.0f / 1024.0f;
-}
-
-int ocean_update_foam(ocean_t* c, uint32_t tile, const ocean_foam* f, float dt)
-{
-    if (!c || !f) return OCEAN_E_INVALID;
-    if (tile != OCEAN_ALL_TILES && tile >= c->tiles) return OCEAN_E_INVALID;
-    if (!std::isfinite(f->threshold) || !std::isfinite(f->gain) || !std::isfinite(f->lifetime) || !std::isfinite(f->spread) || !std::isfinite(f->cutoff) ||
-        !std::isfinite(dt))
-        return OCEAN_E_INVALID;
-    if (!(f->lifetime > 0.0f) || f->spread < 0.0f || f->spread > 1.0f || f->cutoff < 0.0f || f->cutoff > 1.0f || dt < 0.0f) return OCEAN_E_INVALID;
-    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
-    const int set = c->last_set;
-    const int mode = c->set_mode[set];              // of the frame that wrote these maps, not of the next one
-    if (mode != OCEAN_MODE_FULL7 && mode != OCEAN_MODE_JACOBIAN) return OCEAN_E_UNSUPPORTED;
-    HIP_TRY(hipSetDevice(c->device));
-    const uint32_t first = tile == OCEAN_ALL_TILES ? 0u : tile, count = tile == OCEAN_ALL_TILES ? c->tiles : 1u;
-    const size_t n2 = (size_t)c->n * c->n;
-    FoamArgs a;
-    a.lambda = nullptr;
-    a.lambda_all = c->set_lambda[set][first];
-    if (mode == OCEAN_MODE_FULL7) {
-        bool uniform = true;
-        for (uint32_t i = first + 1; i < first + count && uniform; ++i) uniform = c->set_lambda[set][i] == a.lambda_all;
-        if (!uniform) {         // per-tile lambdas: the device copy is replaced only when they change, and then nothing in flight may still read it
-            if (c->foam_lambda_host != c->set_lambda[set]) {
-                SYNC_ALL(c);
-                if (!c->foam_lambda) HIP_TRY(hipMalloc(&c->foam_lambda, c->tiles * sizeof(float)));
-                HIP_TRY(hipMemcpy(c->foam_lambda, c->set_lambda[set].data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
-                c->foam_lambda_host = c->set_lambda[set];
-            }
-            a.lambda = c->foam_lambda + first;
-        }
-    }
-    hipStream_t st = stream_of(c, set);             // ordered after the frame that wrote these maps
-    CONSUMER_BEGIN(c, st);
-    { int rc_ = alloc_foam(c, st); if (rc_) return rc_; }
-    const float* src = c->foam[c->foam_cur];
-    float* dst = c->foam[c->foam_cur ^ 1];
-    const float4* maps = mode == OCEAN_MODE_JACOBIAN ? (c->ext_disp ? c->ext_disp : c->dispN[set]) : (c->ext_nrm ? c->ext_nrm : c->nrmN[set]);
-    a.map = maps + first * n2;
-    a.src = src + first * n2;
-    a.dst = dst + first * n2;
-    a.tile_texels = n2;
-    a.threshold = f->threshold; a.gain = f->gain; a.spread = f->spread; a.cutoff = f->cutoff;
-    a.decay = (float)std::exp(-(double)dt / (double)f->lifetime);
-    a.n = (int)c->n;
-    a.log2_groups = 0;
-    while ((4u << a.log2_groups) < c->n) ++a.log2_groups;
-    a.rows = (int)foam_band_rows(c, count);
-    const dim3 grid(foam_blocks(c->n, (unsigned)a.rows), count);
-    if (mode == OCEAN_MODE_JACOBIAN) hipLaunchKernelGGL(k_foam_update<FOAM_FROM_JACOBIAN>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_foam_update<FOAM_FROM_NORMALS>, grid, dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    // the tiles that were not selected keep their state in the buffer that is current from now on
-    if (first > 0) HIP_TRY(hipMemcpyAsync(dst, src, first * n2 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (first + count < c->tiles)
-        HIP_TRY(hipMemcpyAsync(dst + (first + count) * n2, src + (first + count) * n2, (c->tiles - first - count) * n2 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    CONSUMER_END(c, st);
-    c->foam_cur ^= 1;
-    c->foam_ready = true;
-    return OCEAN_OK;
-}
-
-int ocean_reset_foam(ocean_t* c)
-{
-    if (!c) return OCEAN_E_INVALID;
-    if (!c->foam[1]) return OCEAN_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream_of(c, c->last_set);
-    CONSUMER_BEGIN(c, st);
-    HIP_TRY(hipMemsetAsync(c->foam[c->foam_cur], 0, (size_t)c->tiles * c->n * c->n * sizeof(float), st));
-    CONSUMER_END(c, st);
-    return OCEAN_OK;
-}
-
-int ocean_read_foam(ocean_t* c, uint32_t tile, float* out)
-{
-    if (!c || !out || tile >= c->tiles) return OCEAN_E_INVALID;
-    if (!c->foam_ready) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
-    const size_t n2 = (size_t)c->n * c->n;
-    HIP_TRY(hipMemcpy(out, c->foam[c->foam_cur] + tile * n2, n2 * sizeof(float), hipMemcpyDeviceToHost));
-    return OCEAN_OK;
-}
-
-int ocean_device_foam(ocean_t* c, void** d_foam)
-{
-    if (!c || !d_foam) return OCEAN_E_INVALID;
-    *d_foam = c->foam_ready ? c->foam[c->foam_cur] : nullptr;
-    return OCEAN_OK;
-}
-
-}  // extern "C"
-
-// Checks and launch arguments shared by the two foam queries: the surface of the query, then the foam of its first tile.
-static int foam_query_args(ocean_ctx* c, const ocean_surface* s, FoamQueryArgs& a)
-{
-    { int rc_ = query_args(c, s, a.q); if (rc_) return rc_; }
-    if (!c->foam_ready) return OCEAN_E_NOT_READY;
-    a.foam = c->foam[c->foam_cur] + s->first_tile * a.q.tile_texels;
-    a.q.out_pos = nullptr; a.q.out_nrm = nullptr;
-    return OCEAN_OK;
-}
-
-static int launch_foam_query(ocean_ctx* c, const FoamQueryArgs& a, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_query_foam, dim3((a.q.points + 255u) / 256u), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return OCEAN_OK;
-}
-
-extern "C" {
-
-int ocean_query_foam(ocean_t* c, const ocean_surface* s, const float* xz, uint32_t points, float* out)
-{
-    FoamQueryArgs a{};
-    { int rc_ = foam_query_args(c, s, a); if (rc_) return rc_; }
-    if (points == 0) return OCEAN_OK;
-    if (!xz || !out) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    if (points > c->foam_query_capacity) {
-        SYNC_ALL(c);
-        if (c->foam_query_buf) (void)hipFree(c->foam_query_buf);
-        c->foam_query_buf = nullptr; c->foam_query_capacity = 0;
-        HIP_TRY(hipMalloc(&c->foam_query_buf, (size_t)points * 6 * sizeof(float)));
-        c->foam_query_capacity = points;
-    }
-    // [results | points]: the float4 array first, so that both are aligned
-    float* d_out = c->foam_query_buf;
-    float* d_xz = d_out + (size_t)points * 4;
-    a.q.xz = reinterpret_cast<const float2*>(d_xz);
-    a.out = reinterpret_cast<float4*>(d_out);
-    a.q.points = points;
-    hipStream_t st = stream_of(c, c->last_set);             // ordered after the frame that wrote these maps and the foam's last update
-    CONSUMER_BEGIN(c, st);
-    HIP_TRY(hipMemcpyAsync(d_xz, xz, (size_t)points * 2 * sizeof(float), hipMemcpyHostToDevice, st));
-    { int rc_ = launch_foam_query(c, a, st); if (rc_) return rc_; }
-    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)points * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-    CONSUMER_END(c, st);
-    HIP_TRY(hipStreamSynchronize(st));
-    return OCEAN_OK;
-}
-
-int ocean_query_foam_device(ocean_t* c, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out)
-{
-    FoamQueryArgs a{};
-    { int rc_ = foam_query_args(c, s, a); if (rc_) return rc_; }
-    if (points == 0) return OCEAN_OK;
-    if (!d_xz || !d_out) return OCEAN_E_INVALID;
-    HIP_TRY(hipSetDevice(c->device));
-    a.q.xz = static_cast<const float2*>(d_xz);
-    a.out = static_cast<float4*>(d_out);
-    a.q.points = points;
-    hipStream_t st = stream_of(c, c->last_set);
-    CONSUMER_BEGIN(c, st);
-    { int rc_ = launch_foam_query(c, a, st); if (rc_) return rc_; }
-    CONSUMER_END(c, st);
-    return OCEAN_OK;
-}
-
 void* ocean_stream(ocean_t* c) { return c ? (void*)stream_of(c, c->last_set) : nullptr; }
 
 int ocean_set_stream(ocean_t* c, void* s)
 {
     if (!c) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     c->user = (hipStream_t)s;          // (last_set stays: the most recent frame's maps and records remain the ones read out)
     return OCEAN_OK;
 }
@@ -1749,7 +1168,7 @@ int ocean_read_spectrum(ocean_t* c, uint32_t tile, float* h0, float* omega)
     if (!c->prepared) return OCEAN_E_NOT_READY;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     // device storage is transposed ([kx index][kz index]); hand back the reference's row-major [m][n]
     const size_t n = c->n;
     if (h0) {
@@ -1774,7 +1193,7 @@ int ocean_read_xi(ocean_t* c, uint32_t tile, float* xi)
     if (!c->prepared || !c->xi) return OCEAN_E_NOT_READY;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     HIP_TRY(hipMemcpy(xi, c->xi + tile * n2, n2 * sizeof(float2), hipMemcpyDeviceToHost));
     return OCEAN_OK;
 }
@@ -1815,7 +1234,7 @@ int ocean_set_pipeline_depth(ocean_t* c, int depth)
 {
     if (!c || depth < 1 || depth > MAXD) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     c->depth = depth;
     return OCEAN_OK;
 }
@@ -1849,7 +1268,7 @@ int ocean_select_streams(ocean_t* c, uint32_t frames, float* us_per_frame)
     //  streams under the default GPU_MAX_HW_QUEUES = 4; other streams created earlier -- a framework's -- shift the mapping, and the
     //  ranking then compares whatever queues the four streams did land on: still a valid order of the context's own streams)
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     constexpr int CAND = 4;
     float us[CAND];
     int rc;
@@ -1890,7 +1309,7 @@ int ocean_time_frames(ocean_t* c, float t0, float dt, int warmup, int frames, fl
     int rc;
     for (int j = 0; j < warmup; ++j)
         if ((rc = enqueue_frame(c, t0 + dt * (float)j, true, nullptr))) return rc;
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     HIP_TRY(hipEventRecord(c->start_ev, stream_of(c, 0)));
     HIP_TRY(hipEventSynchronize(c->start_ev));
     for (int j = 0; j < frames; ++j)
@@ -1898,7 +1317,7 @@ int ocean_time_frames(ocean_t* c, float t0, float dt, int warmup, int frames, fl
     // the two chains are independent: the timed region ends when the later one does
     const int nstreams = c->user ? 1 : MAXD;
     for (int i = 0; i < nstreams; ++i) HIP_TRY(hipEventRecord(c->end_ev[i], stream_of(c, i)));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     float ms = 0.f;
     for (int i = 0; i < nstreams; ++i) {
         float m = 0.f;
@@ -1945,7 +1364,7 @@ int ocean_time_frames(ocean_t* c, float t0, float dt, int warmup, int frames, fl
                 if ((rc = collect(set))) return rc;
             }
         }
-        SYNC_ALL(c);
+        OCEAN_TRY(sync_all(c));
         for (int k = 0; k < 3; ++k) ms_kernel[k] = (float)(acc[k] / (double)(counted > 0 ? counted : 1));
     }
     return OCEAN_OK;
@@ -1958,7 +1377,7 @@ extern "C" int ocean_debug_clockprobe(ocean_t* c, int enable, unsigned long long
 {
     if (!c) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     const size_t bytes = (size_t)ocean::CLOCKPROBE_LAUNCHES * ocean::CLOCKPROBE_WGS * 4 * sizeof(unsigned long long);
     if (enable && !c->stamps) {
         HIP_TRY(hipMalloc(&c->stamps, bytes));
@@ -2099,7 +1518,7 @@ int ocean_comm_init(ocean_t* c, int nranks, int rank, const void* id_in)
     if (!c || !id_in || nranks < 1 || rank < 0 || rank >= nranks) return OCEAN_E_INVALID;
     if (!rccl().ok) return OCEAN_E_COMM;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     comm_release(c);
     ncclUniqueId id;
     std::memcpy(&id, id_in, sizeof(id));
@@ -2129,7 +1548,7 @@ int ocean_comm_destroy(ocean_t* c)
 {
     if (!c) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    SYNC_ALL(c);
+    OCEAN_TRY(sync_all(c));
     comm_release(c);
     return OCEAN_OK;
 }
@@ -2142,12 +1561,12 @@ static int gather_impl(ocean_ctx* c, int root, void* d_recv_disp, void* d_recv_n
     if (c->comm_rank == root && (!d_recv_disp || !d_recv_nrm)) return OCEAN_E_INVALID;
     if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
     HIP_TRY(hipSetDevice(c->device));
-    { int rc_ = check_fault(c); if (rc_) return rc_; }                        // (as in consumer_begin)
+    OCEAN_TRY(check_fault(c));                        // (as in consumer_begin)
     const int set = c->last_set;
     const size_t texels = (size_t)c->tiles * c->n * c->n;
     const size_t count = texels * 4;                                          // elements per map array per rank
-    const void* d = c->ext_disp ? c->ext_disp : c->dispN[set];
-    const void* q = c->ext_nrm ? c->ext_nrm : c->nrmN[set];
+    const void* d = maps_of(c, set).disp;
+    const void* q = maps_of(c, set).nrm;
     if (half) {     // convert on the frame's own stream, behind the frame: 16 instead of 32 bytes per texel on the wire
         for (auto& p : c->pack_half[set]) if (!p) HIP_TRY(hipMalloc(&p, texels * sizeof(uint2)));
         const unsigned blocks = (unsigned)((texels + 255) / 256 < 65535 ? (texels + 255) / 256 : 65535);

@@ -1,0 +1,530 @@
+// ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
+// cascades, mip chain, surface query, ray cast, persistent foam) and the device memory those calls own.  Their kernels: ocean_consumer_kernels.h,
+// ocean_foam_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+#include <cmath>
+
+#include "ocean_ctx.h"
+#include "ocean_foam_kernels.h"     // (includes ocean_consumer_kernels.h)
+
+using namespace ocean;
+
+// ---- the host path every consumer shares ---------------------------------------------------------------------------------------------------
+// What a consumer reads: the most recently enqueued frame.  Its maps and height keys from tile `first_tile` on, and the stream it was enqueued
+// on -- the consumer's launch goes there, so it is ordered after the frame that wrote these maps.
+struct LastFrame {
+    const float4* disp;
+    const float4* nrm;
+    const unsigned* minmax;
+    hipStream_t st;
+    int set;                // the frame's chain: c->set_lambda / set_length / set_mode[set] describe it
+    size_t n2;              // texels per tile
+};
+static int last_frame(const ocean_ctx* c, uint32_t first_tile, LastFrame& f)
+{
+    if (!c->prepared || !c->have_frame) return OCEAN_E_NOT_READY;
+    f.set = c->last_set;
+    f.n2 = (size_t)c->n * c->n;
+    f.disp = maps_of(c, f.set).disp + first_tile * f.n2;
+    f.nrm = maps_of(c, f.set).nrm + first_tile * f.n2;
+    f.minmax = c->minmax[f.set] + 2 * first_tile;
+    f.st = stream_of(c, f.set);
+    return OCEAN_OK;
+}
+
+// The consumer kernels write context-wide output buffers and run on the stream of the frame they read.  At pipeline depth > 1 consecutive
+// consumer calls land on different, mutually unordered chain streams: each call first makes its stream wait for the previous consumer launch,
+// so that two of them never write those buffers at once.
+static int consumer_begin(ocean_ctx* c, hipStream_t st)
+{
+    // (a frame whose in-launch wait has given up by now is recovered before anything consumes it; one that gives up later is reported
+    //  by the next wait / synchronisation: recover_fault)
+    OCEAN_TRY(check_fault(c));
+    if (c->consumer_pending && c->consumer_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->consumer_ev, 0));
+    return OCEAN_OK;
+}
+static int consumer_end(ocean_ctx* c, hipStream_t st)
+{
+    if (!c->consumer_ev) HIP_TRY(hipEventCreateWithFlags(&c->consumer_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->consumer_ev, st));
+    c->consumer_stream = st;
+    c->consumer_pending = true;
+    return OCEAN_OK;
+}
+
+// Replaces a context-wide buffer (or two that grow together: b may be null) by one of `bytes` each.  Nothing in flight may still use the old
+// one, so everything is drained first; the capacity is zero while there is no buffer, and `invalidate` drops whatever "ready" state described
+// the old contents at the moment they are freed -- a growth that fails half way leaves nothing that claims to be readable.
+template <class T, class Cap, class Invalidate>
+static int regrow(ocean_ctx* c, T** a, T** b, size_t bytes, Cap& capacity, Cap want, Invalidate invalidate)
+{
+    OCEAN_TRY(sync_all(c));
+    for (T** p : {a, b})
+        if (p && *p) { (void)hipFree(*p); *p = nullptr; }
+    capacity = 0;
+    invalidate();
+    for (T** p : {a, b})
+        if (p) HIP_TRY(hipMalloc(p, bytes));
+    capacity = want;
+    return OCEAN_OK;
+}
+
+template <class T>
+static void free_and_null(T*& p)
+{
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
+
+void ocean_consumers_release(ocean_ctx* c, bool everything)
+{
+    free_and_null(c->staging); c->staging_bytes = 0;
+    for (float*& f : c->foam) free_and_null(f);
+    free_and_null(c->foam_lambda); c->foam_lambda_host.clear();
+    c->foam_cur = 0; c->foam_ready = false;
+    // the grid and mip buffers survive a new tile size (the grid's does not depend on it, ocean_build_mips re-allocates for mips_n != n),
+    // their contents do not: they were made from maps that are gone
+    c->mips_ready = false; c->grid_vertices = 0;
+    if (!everything) return;
+    free_and_null(c->grid_pos); free_and_null(c->grid_nrm); c->grid_capacity = 0;
+    free_and_null(c->mips_disp); free_and_null(c->mips_nrm); c->mips_n = 0;
+    if (c->consumer_ev) { (void)hipEventDestroy(c->consumer_ev); c->consumer_ev = nullptr; }
+    c->consumer_pending = false;
+}
+
+// ---- vertex stage and mip chain ------------------------------------------------------------------------------------------------------------
+// Readiness, the output buffers for a grid of grid_size quads per side, and the launch arguments of the vertex stage from tile first_tile on.
+static int grid_args(ocean_ctx* c, uint32_t first_tile, uint32_t grid_size, float vertex_distance, float uv_scale, float choppy,
+                     LastFrame& f, GridArgs& g, uint32_t& verts)
+{
+    OCEAN_TRY(last_frame(c, first_tile, f));
+    HIP_TRY(hipSetDevice(c->device));
+    verts = (grid_size + 1) * (grid_size + 1);
+    if (verts > c->grid_capacity)
+        OCEAN_TRY(regrow(c, &c->grid_pos, &c->grid_nrm, (size_t)verts * sizeof(float4), c->grid_capacity, verts, [c] { c->grid_vertices = 0; }));
+    g.disp = f.disp; g.nrm = f.nrm; g.minmax = f.minmax;
+    g.positions = c->grid_pos; g.normals = c->grid_nrm;
+    g.n = (int)c->n; g.grid = (int)grid_size;
+    g.vertex_distance = vertex_distance; g.uv_scale = uv_scale; g.choppy = choppy;
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_displace_grid(ocean_t* c, uint32_t tile, uint32_t grid_size, float vertex_distance, float uv_scale, float choppy)
+{
+    if (!c || tile >= c->tiles || grid_size == 0 || grid_size > 8192) return OCEAN_E_INVALID;
+    LastFrame f;
+    GridArgs g;
+    uint32_t verts;
+    OCEAN_TRY(grid_args(c, tile, grid_size, vertex_distance, uv_scale, choppy, f, g, verts));
+    OCEAN_TRY(consumer_begin(c, f.st));
+    hipLaunchKernelGGL(k_displace_grid, dim3((verts + 255) / 256), dim3(256), 0, f.st, g);
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->grid_vertices = verts;
+    return OCEAN_OK;
+}
+
+int ocean_displace_grid_cascades(ocean_t* c, uint32_t first_tile, uint32_t count, uint32_t grid_size, float vertex_distance,
+                                 const float* uv_scales, float choppy)
+{
+    if (!c || !uv_scales || count == 0 || count > (uint32_t)OCEAN_MAX_CASCADES || first_tile >= c->tiles || first_tile + count > c->tiles ||
+        grid_size == 0 || grid_size > 8192)
+        return OCEAN_E_INVALID;
+    LastFrame f;
+    CascadeArgs a;
+    uint32_t verts;
+    OCEAN_TRY(grid_args(c, first_tile, grid_size, vertex_distance, 1.0f, choppy, f, a.g, verts));
+    a.count = (int)count; a.tile_texels = f.n2;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) a.uv_scale[i] = i < count ? uv_scales[i] : 0.0f;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    hipLaunchKernelGGL(k_displace_grid_cascades, dim3((verts + 255) / 256), dim3(256), 0, f.st, a);
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->grid_vertices = verts;
+    return OCEAN_OK;
+}
+
+int ocean_read_grid(ocean_t* c, float* positions, float* normals)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (!c->grid_vertices) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    if (positions) HIP_TRY(hipMemcpy(positions, c->grid_pos, (size_t)c->grid_vertices * sizeof(float4), hipMemcpyDeviceToHost));
+    if (normals) HIP_TRY(hipMemcpy(normals, c->grid_nrm, (size_t)c->grid_vertices * sizeof(float4), hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+int ocean_device_grid(ocean_t* c, void** d_positions, void** d_normals, uint32_t* vertices)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (d_positions) *d_positions = c->grid_pos;
+    if (d_normals) *d_normals = c->grid_nrm;
+    if (vertices) *vertices = c->grid_vertices;
+    return OCEAN_OK;
+}
+
+size_t ocean_mip_texels(uint32_t n) { return ((size_t)n * n - 1) / 3; }      // sum of (n >> l)^2, l = 1 .. log2 n
+
+int ocean_build_mips(ocean_t* c, uint32_t tile)
+{
+    if (!c || tile >= c->tiles) return OCEAN_E_INVALID;
+    LastFrame f;
+    OCEAN_TRY(last_frame(c, tile, f));
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t n = c->n;
+    if (c->mips_n != n)
+        OCEAN_TRY(regrow(c, &c->mips_disp, &c->mips_nrm, ocean_mip_texels(n) * sizeof(float4), c->mips_n, n, [c] { c->mips_ready = false; }));
+    MipArgs m;
+    m.src[0] = f.disp; m.src[1] = f.nrm;
+    m.dst[0] = c->mips_disp; m.dst[1] = c->mips_nrm;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    for (uint32_t w = n / 2; w >= 1; w /= 2) {
+        m.w = (int)w;
+        hipLaunchKernelGGL(k_mip_level, dim3((w * w + 255) / 256, 2), dim3(256), 0, f.st, m);
+        m.src[0] = m.dst[0]; m.src[1] = m.dst[1];
+        m.dst[0] += (size_t)w * w; m.dst[1] += (size_t)w * w;
+    }
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->mips_ready = true;
+    return OCEAN_OK;
+}
+
+int ocean_read_mips(ocean_t* c, float* disp_mips, float* nrm_mips)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (!c->mips_ready) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    const size_t bytes = ocean_mip_texels(c->mips_n) * sizeof(float4);
+    if (disp_mips) HIP_TRY(hipMemcpy(disp_mips, c->mips_disp, bytes, hipMemcpyDeviceToHost));
+    if (nrm_mips) HIP_TRY(hipMemcpy(nrm_mips, c->mips_nrm, bytes, hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+int ocean_device_mips(ocean_t* c, void** d_disp_mips, void** d_nrm_mips, uint32_t* levels)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (d_disp_mips) *d_disp_mips = c->mips_ready ? c->mips_disp : nullptr;
+    if (d_nrm_mips) *d_nrm_mips = c->mips_ready ? c->mips_nrm : nullptr;
+    if (levels) { uint32_t l = 0; for (uint32_t w = c->mips_n; c->mips_ready && w > 1; w /= 2) ++l; *levels = l; }
+    return OCEAN_OK;
+}
+
+}  // extern "C"
+
+// ---- query-like calls: surface query, ray cast, foam query ---------------------------------------------------------------------------------
+// Each has a host-blocking form (host arrays in and out, through the staging buffer) and a _device twin (device arrays, stream-ordered), and
+// each is: an argument builder (validation, then readiness: *_args below), the checks of call_checks, a launch function that binds the device
+// arrays of `count` items into the arguments and launches.  out1 is null where a call has one output.
+template <class Args>
+using LaunchFn = int (*)(Args& a, uint32_t count, const void* d_in, void* d_out0, void* d_out1, hipStream_t st);
+
+// Behind the builder's verdict `rc`, in the order the callers rely on: nothing to do for no items -- before the pointers are looked at --,
+// then the pointers.  (A caller returns OCEAN_OK itself when count == 0.)
+static int call_checks(ocean_ctx* c, int rc, uint32_t count, bool null_pointer)
+{
+    if (rc || count == 0) return rc;
+    if (null_pointer) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    return OCEAN_OK;
+}
+
+template <class Args>
+static int device_call(ocean_ctx* c, int rc, const LastFrame& f, Args& a, LaunchFn<Args> launch, uint32_t count,
+                       const void* d_in, void* d_out0, void* d_out1, int outs)
+{
+    OCEAN_TRY(call_checks(c, rc, count, !d_in || !d_out0 || (outs == 2 && !d_out1)));
+    if (count == 0) return OCEAN_OK;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    OCEAN_TRY(launch(a, count, d_in, d_out0, d_out1, f.st));
+    return consumer_end(c, f.st);
+}
+
+// The host-blocking form: in_floats floats per item in, `outs` float4 per item out, staged in c->staging and copied on the frame's stream,
+// which is synchronised before the call returns (what lets the three calls share that buffer: ocean_ctx.h).
+template <class Args>
+static int staged_call(ocean_ctx* c, int rc, const LastFrame& f, Args& a, LaunchFn<Args> launch, uint32_t count,
+                       const float* in, size_t in_floats, float* out0, float* out1, int outs)
+{
+    OCEAN_TRY(call_checks(c, rc, count, !in || !out0 || (outs == 2 && !out1)));
+    if (count == 0) return OCEAN_OK;
+    const size_t out_bytes = (size_t)count * sizeof(float4), in_bytes = (size_t)count * in_floats * sizeof(float);
+    const size_t bytes = (size_t)outs * out_bytes + in_bytes;
+    if (bytes > c->staging_bytes) OCEAN_TRY(regrow(c, &c->staging, (void**)nullptr, bytes, c->staging_bytes, bytes, [] {}));
+    // [outputs | input]: the float4 arrays first, so that every array is 16-byte aligned
+    char* d_out0 = static_cast<char*>(c->staging);
+    char* d_out1 = outs == 2 ? d_out0 + out_bytes : nullptr;
+    char* d_in = d_out0 + (size_t)outs * out_bytes;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, f.st));
+    OCEAN_TRY(launch(a, count, d_in, d_out0, d_out1, f.st));
+    HIP_TRY(hipMemcpyAsync(out0, d_out0, out_bytes, hipMemcpyDeviceToHost, f.st));
+    if (outs == 2) HIP_TRY(hipMemcpyAsync(out1, d_out1, out_bytes, hipMemcpyDeviceToHost, f.st));
+    OCEAN_TRY(consumer_end(c, f.st));
+    HIP_TRY(hipStreamSynchronize(f.st));
+    return OCEAN_OK;
+}
+
+// Checks and launch arguments of the surface every query-like call reads (the device pointers are bound by the launch function).
+static int query_args(ocean_ctx* c, const ocean_surface* s, LastFrame& f, QueryArgs& a)
+{
+    if (!c || !s || s->cascades == 0 || s->cascades > (uint32_t)OCEAN_MAX_CASCADES || s->first_tile >= c->tiles ||
+        s->cascades > c->tiles - s->first_tile || s->grid_size == 0 || s->iterations > 32)
+        return OCEAN_E_INVALID;
+    OCEAN_TRY(last_frame(c, s->first_tile, f));
+    a.disp = f.disp; a.nrm = f.nrm; a.minmax = f.minmax;
+    a.tile_texels = f.n2;
+    a.n = (int)c->n;
+    a.count = (int)s->cascades;
+    a.iterations = s->iterations ? (int)s->iterations : 8;
+    a.grid = (float)s->grid_size;
+    a.half = (float)(s->grid_size / 2);
+    a.vertex_distance = s->vertex_distance;
+    a.choppy = s->choppy;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) {
+        a.uv_scale[i] = i < s->cascades ? s->uv_scales[i] : 0.0f;
+        a.gain[i] = 0.0f;
+        if (i < s->cascades) {      // lambda_c * (s_c * L_c / (grid * vertex_distance)) of the frame that wrote tile c's maps
+            const uint32_t tile = s->first_tile + i;
+            a.gain[i] = c->set_lambda[f.set][tile] * (s->uv_scales[i] * c->set_length[f.set][tile] / (a.grid * s->vertex_distance));
+        }
+    }
+    return OCEAN_OK;
+}
+
+static int launch_query(QueryArgs& a, uint32_t points, const void* d_xz, void* d_out_pos, void* d_out_nrm, hipStream_t st)
+{
+    a.xz = static_cast<const float2*>(d_xz);
+    a.out_pos = static_cast<float4*>(d_out_pos);
+    a.out_nrm = static_cast<float4*>(d_out_nrm);
+    a.points = points;
+    hipLaunchKernelGGL(k_query_surface, dim3((a.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+// ... of the ray cast: the surface of the query, then the ray settings.
+static int raycast_args(ocean_ctx* c, const ocean_surface* s, const ocean_raycast* r, LastFrame& f, RaycastArgs& a)
+{
+    if (!c || !s || !r || !(r->max_distance > 0.0f) || !std::isfinite(r->max_distance) || r->steps > 4096 || r->refine > 8)
+        return OCEAN_E_INVALID;
+    OCEAN_TRY(query_args(c, s, f, a.q));
+    a.max_distance = r->max_distance;
+    a.steps = r->steps ? (int)r->steps : 64;
+    a.refine = r->refine ? (int)r->refine : 3;
+    return OCEAN_OK;
+}
+
+static int launch_raycast(RaycastArgs& a, uint32_t count, const void* d_rays, void* d_out_hit, void* d_out_nrm, hipStream_t st)
+{
+    a.rays = static_cast<const float*>(d_rays);
+    a.out_hit = static_cast<float4*>(d_out_hit);
+    a.out_nrm = static_cast<float4*>(d_out_nrm);
+    a.count = count;
+    const unsigned rays_per_block = 256u / RAYCAST_LANES;
+    hipLaunchKernelGGL(k_raycast_surface, dim3((unsigned)(((uint64_t)a.count + rays_per_block - 1u) / rays_per_block)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+// ... of the foam query: the surface of the query, then the foam of its first tile.
+static int foam_query_args(ocean_ctx* c, const ocean_surface* s, LastFrame& f, FoamQueryArgs& a)
+{
+    OCEAN_TRY(query_args(c, s, f, a.q));
+    if (!c->foam_ready) return OCEAN_E_NOT_READY;
+    a.foam = c->foam[c->foam_cur] + s->first_tile * a.q.tile_texels;
+    a.q.out_pos = nullptr; a.q.out_nrm = nullptr;
+    return OCEAN_OK;
+}
+
+static int launch_foam_query(FoamQueryArgs& a, uint32_t points, const void* d_xz, void* d_out, void*, hipStream_t st)
+{
+    a.q.xz = static_cast<const float2*>(d_xz);
+    a.out = static_cast<float4*>(d_out);
+    a.q.points = points;
+    hipLaunchKernelGGL(k_query_foam, dim3((a.q.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_query_surface(ocean_t* c, const ocean_surface* s, const float* xz, uint32_t points, float* out_pos, float* out_nrm)
+{
+    LastFrame f;
+    QueryArgs a;
+    return staged_call(c, query_args(c, s, f, a), f, a, launch_query, points, xz, 2, out_pos, out_nrm, 2);
+}
+
+int ocean_query_surface_device(ocean_t* c, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out_pos, void* d_out_nrm)
+{
+    LastFrame f;
+    QueryArgs a;
+    return device_call(c, query_args(c, s, f, a), f, a, launch_query, points, d_xz, d_out_pos, d_out_nrm, 2);
+}
+
+int ocean_raycast_surface(ocean_t* c, const ocean_surface* s, const ocean_raycast* r, const float* rays, uint32_t count,
+                          float* out_hit, float* out_nrm)
+{
+    LastFrame f;
+    RaycastArgs a{};
+    return staged_call(c, raycast_args(c, s, r, f, a), f, a, launch_raycast, count, rays, 6, out_hit, out_nrm, 2);
+}
+
+int ocean_raycast_surface_device(ocean_t* c, const ocean_surface* s, const ocean_raycast* r, const void* d_rays, uint32_t count,
+                                 void* d_out_hit, void* d_out_nrm)
+{
+    LastFrame f;
+    RaycastArgs a{};
+    return device_call(c, raycast_args(c, s, r, f, a), f, a, launch_raycast, count, d_rays, d_out_hit, d_out_nrm, 2);
+}
+
+}  // extern "C"
+
+// ---- persistent foam (include/ocean_consumers.h) -----------------------------------------------------------------------------------------
+// Both buffers or none (as alloc_jacobian): zero-filled on the stream of the update that asked for them.
+static int alloc_foam(ocean_ctx* c, hipStream_t st)
+{
+    if (c->foam[1]) return OCEAN_OK;               // the second of the two: complete
+    const size_t bytes = (size_t)c->tiles * c->n * c->n * sizeof(float);
+    for (int k = 0; k < 2; ++k) {
+        if (c->foam[k]) { (void)hipFree(c->foam[k]); c->foam[k] = nullptr; }       // leftovers of an earlier failed attempt
+        if (hipMalloc(&c->foam[k], bytes) != hipSuccess || hipMemsetAsync(c->foam[k], 0, bytes, st) != hipSuccess) {
+            for (int j = 0; j <= k; ++j) if (c->foam[j]) { (void)hipFree(c->foam[j]); c->foam[j] = nullptr; }
+            g_last_hip = (int)hipGetLastError();
+            return OCEAN_E_NOMEM;
+        }
+    }
+    c->foam_cur = 0; c->foam_ready = false;
+    return OCEAN_OK;
+}
+
+// Rows per band of k_foam_update's row walk: as long as the launch still has four waves for every compute unit (a band re-reads two rows of F).
+static unsigned foam_band_rows(const ocean_ctx* c, uint32_t tiles)
+{
+    const double waves_per_row = (double)tiles * c->n * c->n / 256.0;
+    unsigned rows = 32;
+    while (rows > 4 && waves_per_row / rows < 4.0 * (c->cu_count > 0 ? c->cu_count : 256)) rows /= 2;
+    return rows < c->n ? rows : c->n;
+}
+
+extern "C" {
+
+void ocean_default_foam(ocean_foam* f)
+{
+    if (!f) return;
+    f->threshold = 0.6f;
+    f->gain = 2.5f;
+    f->lifetime = 4.0f;
+    f->spread = 0.25f;
+    f->cutoff = 1.0f / 1024.0f;
+}
+
+int ocean_update_foam(ocean_t* c, uint32_t tile, const ocean_foam* f, float dt)
+{
+    if (!c || !f) return OCEAN_E_INVALID;
+    if (tile != OCEAN_ALL_TILES && tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!std::isfinite(f->threshold) || !std::isfinite(f->gain) || !std::isfinite(f->lifetime) || !std::isfinite(f->spread) || !std::isfinite(f->cutoff) ||
+        !std::isfinite(dt))
+        return OCEAN_E_INVALID;
+    if (!(f->lifetime > 0.0f) || f->spread < 0.0f || f->spread > 1.0f || f->cutoff < 0.0f || f->cutoff > 1.0f || dt < 0.0f) return OCEAN_E_INVALID;
+    const uint32_t first = tile == OCEAN_ALL_TILES ? 0u : tile, count = tile == OCEAN_ALL_TILES ? c->tiles : 1u;
+    LastFrame fr;
+    OCEAN_TRY(last_frame(c, first, fr));
+    const int set = fr.set;
+    const int mode = c->set_mode[set];              // of the frame that wrote these maps, not of the next one
+    if (mode != OCEAN_MODE_FULL7 && mode != OCEAN_MODE_JACOBIAN) return OCEAN_E_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n2 = fr.n2;
+    FoamArgs a;
+    a.lambda = nullptr;
+    a.lambda_all = c->set_lambda[set][first];
+    if (mode == OCEAN_MODE_FULL7) {
+        bool uniform = true;
+        for (uint32_t i = first + 1; i < first + count && uniform; ++i) uniform = c->set_lambda[set][i] == a.lambda_all;
+        if (!uniform) {         // per-tile lambdas: the device copy is replaced only when they change, and then nothing in flight may still read it
+            if (c->foam_lambda_host != c->set_lambda[set]) {
+                OCEAN_TRY(sync_all(c));
+                if (!c->foam_lambda) HIP_TRY(hipMalloc(&c->foam_lambda, c->tiles * sizeof(float)));
+                HIP_TRY(hipMemcpy(c->foam_lambda, c->set_lambda[set].data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
+                c->foam_lambda_host = c->set_lambda[set];
+            }
+            a.lambda = c->foam_lambda + first;
+        }
+    }
+    hipStream_t st = fr.st;
+    OCEAN_TRY(consumer_begin(c, st));
+    OCEAN_TRY(alloc_foam(c, st));
+    const float* src = c->foam[c->foam_cur];
+    float* dst = c->foam[c->foam_cur ^ 1];
+    a.map = mode == OCEAN_MODE_JACOBIAN ? fr.disp : fr.nrm;
+    a.src = src + first * n2;
+    a.dst = dst + first * n2;
+    a.tile_texels = n2;
+    a.threshold = f->threshold; a.gain = f->gain; a.spread = f->spread; a.cutoff = f->cutoff;
+    a.decay = (float)std::exp(-(double)dt / (double)f->lifetime);
+    a.n = (int)c->n;
+    a.log2_groups = 0;
+    while ((4u << a.log2_groups) < c->n) ++a.log2_groups;
+    a.rows = (int)foam_band_rows(c, count);
+    const dim3 grid(foam_blocks(c->n, (unsigned)a.rows), count);
+    if (mode == OCEAN_MODE_JACOBIAN) hipLaunchKernelGGL(k_foam_update<FOAM_FROM_JACOBIAN>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_foam_update<FOAM_FROM_NORMALS>, grid, dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    // the tiles that were not selected keep their state in the buffer that is current from now on
+    if (first > 0) HIP_TRY(hipMemcpyAsync(dst, src, first * n2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (first + count < c->tiles)
+        HIP_TRY(hipMemcpyAsync(dst + (first + count) * n2, src + (first + count) * n2, (c->tiles - first - count) * n2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    OCEAN_TRY(consumer_end(c, st));
+    c->foam_cur ^= 1;
+    c->foam_ready = true;
+    return OCEAN_OK;
+}
+
+int ocean_reset_foam(ocean_t* c)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (!c->foam[1]) return OCEAN_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, c->last_set);
+    OCEAN_TRY(consumer_begin(c, st));
+    HIP_TRY(hipMemsetAsync(c->foam[c->foam_cur], 0, (size_t)c->tiles * c->n * c->n * sizeof(float), st));
+    return consumer_end(c, st);
+}
+
+int ocean_read_foam(ocean_t* c, uint32_t tile, float* out)
+{
+    if (!c || !out || tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!c->foam_ready) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    const size_t n2 = (size_t)c->n * c->n;
+    HIP_TRY(hipMemcpy(out, c->foam[c->foam_cur] + tile * n2, n2 * sizeof(float), hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+int ocean_device_foam(ocean_t* c, void** d_foam)
+{
+    if (!c || !d_foam) return OCEAN_E_INVALID;
+    *d_foam = c->foam_ready ? c->foam[c->foam_cur] : nullptr;
+    return OCEAN_OK;
+}
+
+int ocean_query_foam(ocean_t* c, const ocean_surface* s, const float* xz, uint32_t points, float* out)
+{
+    LastFrame f;
+    FoamQueryArgs a{};
+    return staged_call(c, foam_query_args(c, s, f, a), f, a, launch_foam_query, points, xz, 2, out, nullptr, 1);
+}
+
+int ocean_query_foam_device(ocean_t* c, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out)
+{
+    LastFrame f;
+    FoamQueryArgs a{};
+    return device_call(c, foam_query_args(c, s, f, a), f, a, launch_foam_query, points, d_xz, d_out, nullptr, 1);
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 // ocean_ctx.h -- the context behind the opaque ocean_t of include/ocean.h, shared by the translation units of
-// libocean_hip.so (ocean_api.hip: the C ABI; frames_*.hip: the per-size frame launchers).
+// libocean_hip.so (ocean_api.hip: the C ABI of ocean.h and ocean_dev.h; ocean_consumers.hip: that of ocean_consumers.h; frames_*.hip: the
+// per-size frame launchers), and the few internals that cross between them (at the end of this file).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -185,18 +186,18 @@ struct ocean_ctx {
     std::vector<float> prep_length;         // [tiles] tile length the most recent ocean_prepare built the spectrum for
     std::vector<float> set_lambda[MAXD];    // [tiles] lambda and tile length of the frame that wrote each chain's maps
     std::vector<float> set_length[MAXD];    //   (recorded when it is enqueued: what ocean_query_surface's Newton step needs)
-    float* query_buf = nullptr;     // ocean_query_surface: staging of the points and results, 10 floats per point (grows on demand)
-    uint32_t query_capacity = 0;    // points it holds
+    // Staging of the host-blocking consumer calls (ocean_query_surface, ocean_raycast_surface, ocean_query_foam): [float4 outputs | input] of
+    // ONE call, grown to the largest request seen.  One buffer serves all three because every user synchronises its stream before it returns:
+    // nothing of an earlier call is in flight when the next one lays its arrays out.  (The grid, mip and foam outputs are handed to the caller
+    // and stay buffers of their own.)
+    void* staging = nullptr;
+    size_t staging_bytes = 0;
     int set_mode[MAXD] = {};                //   ... and its OCEAN_MODE_*: which Jacobian ocean_update_foam finds in the maps
     float* foam[2] = {};            // persistent foam (ocean_update_foam): two buffers [tiles][N][N] that alternate, allocated on first use
     int foam_cur = 0;               // the one that holds the state after the most recently enqueued update
     bool foam_ready = false;        // an update has been enqueued since the last ocean_prepare
     float* foam_lambda = nullptr;   // [tiles] lambdas of a FULL7 frame whose tiles differ (uploaded when they change: foam_lambda_host)
     std::vector<float> foam_lambda_host;
-    float* foam_query_buf = nullptr;    // ocean_query_foam: staging of the points and results, 6 floats per point (grows on demand)
-    uint32_t foam_query_capacity = 0;
-    float* ray_buf = nullptr;       // ocean_raycast_surface: staging of the rays and results, 14 floats per ray (grows on demand)
-    uint32_t ray_capacity = 0;      // rays it holds
     unsigned long long* stamps = nullptr;   // diagnostic builds only
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
@@ -229,6 +230,35 @@ struct ocean_ctx {
 
 
 inline hipStream_t stream_of(const ocean_ctx* c, int set) { return c->user ? c->user : c->own[set]; }
+
+// The maps a frame of chain `set` writes and everything behind it reads: the caller-bound ones (ocean_bind_output / _dmabuf) or the set's own.
+struct OceanMaps { float4* disp; float4* nrm; };
+inline OceanMaps maps_of(const ocean_ctx* c, int set) { return {c->ext_disp ? c->ext_disp : c->dispN[set], c->ext_nrm ? c->ext_nrm : c->nrmN[set]}; }
+
+// ---- what crosses between ocean_api.hip and ocean_consumers.hip (nothing else does) -----------------------------------------------------
+namespace ocean { extern thread_local int g_last_hip; }     // ocean_last_hip_error(); defined in ocean_api.hip
+
+#define HIP_TRY(expr)                                   \
+    do {                                                \
+        hipError_t e_ = (expr);                         \
+        if (e_ != hipSuccess) {                         \
+            ocean::g_last_hip = (int)e_;                \
+            (void)hipGetLastError();                    \
+            return e_ == hipErrorOutOfMemory ? OCEAN_E_NOMEM : OCEAN_E_HIP; \
+        }                                               \
+    } while (0)
+// the same for the library's own codes: OCEAN_OK goes on, anything else is returned
+#define OCEAN_TRY(expr)                                 \
+    do {                                                \
+        const int rc_ = (expr);                         \
+        if (rc_) return rc_;                            \
+    } while (0)
+
+int sync_all(ocean_ctx* c);         // drains every stream of the context, recovers a frame whose in-launch wait gave up, empties the pipeline bookkeeping
+int check_fault(ocean_ctx* c);      // only that recovery, where one is due (before anything consumes a frame)
+// The consumers' device memory has one owner, ocean_consumers.hip.  everything = false (ocean_set_tile_size: free_device): what depends on the
+// tile size -- staging, foam -- and the "ready" state of what does not; true (ocean_destroy): the grid, the mips and the consumer event as well.
+void ocean_consumers_release(ocean_ctx* c, bool everything);
 
 // One frame = three launches on `st` (ocean_launch.h); one entry point per group of tile sizes, each compiled in its
 // own translation unit (frames_*.hip) so that the library builds in parallel.  stream_maps: bit 0 normal map and

@@ -1,8 +1,8 @@
-// ocean_foam_kernels.h -- persistent foam (include/ocean_consumers.h: ocean_update_foam, ocean_query_foam), compiled into ocean_api.hip only.
+// ocean_foam_kernels.h -- persistent foam (include/ocean_consumers.h: ocean_update_foam, ocean_query_foam), compiled into ocean_consumers.hip only.
 // A per-tile coverage field F[tiles][N][N] in [0, 1] in the maps' texel layout: generated where the Jacobian of the frame's maps falls under
 // a threshold, blended towards its 3 x 3 binomial, decayed, cut off.  The header states the step; tests/foam.py repeats it in numpy.
 #pragma once
-#include "ocean_aux_kernels.h"
+#include "ocean_consumer_kernels.h"
 
 namespace ocean {
 
