@@ -102,8 +102,10 @@ int ocean_query_surface_device(ocean_t* ctx, const ocean_surface* s, const void*
  * (x, z).  fp32 throughout, no contraction, in this order (the test suite repeats it step for step):
  *   Direction   len = sqrtf((dx*dx + dy*dy) + dz*dz); a zero or non-finite len is a miss; d = (dx/len, dy/len, dz/len).
  *   Gap         p(t) = (o.x + t*d.x, o.y + t*d.y, o.z + t*d.z),  f(t) = p(t).y - H(p(t).x, p(t).z): the height above the water.
- *   Slab        Hmax = 1.001f * (amp_0 + amp_1 + ...) (sum from 0.0f in cascade order; amp_c is the largest magnitude of tile
- *               c's height keys, the amplitude the query scales heights with), so every height lies in [-Hmax, Hmax].
+ *   Slab        Hmax = fmaxf(1.001f * (amp_0 + amp_1 + ...), 1e-3f) (sum from 0.0f in cascade order; amp_c is the largest magnitude
+ *               of tile c's height keys, the amplitude the query scales heights with), so every height lies in [-Hmax, Hmax].
+ *               The floor of 1 mm is for a flat sea (amp = FLT_MIN): without it the slab has no thickness, every sample of the
+ *               march is the one point o.y + t0*d.y, and its rounding decides between hit and miss.
  *               If o.y <= -Hmax the origin is under water (below).  Otherwise [0, max_distance] is clipped to the slab:
  *                 d.y < 0:   t0 = fmaxf(0, (Hmax - o.y) / d.y),   t1 = fminf(max_distance, (-Hmax - o.y) / d.y)
  *                 d.y > 0:   t0 = fmaxf(0, (-Hmax - o.y) / d.y),  t1 = fminf(max_distance, (Hmax - o.y) / d.y)

@@ -124,3 +124,12 @@ def query_foam(foams, disps, nrms, amps, lambdas, lengths, uv_scales, grid, vert
     ex, ez = (rx + dx) - qx, (rz + dz) - qz
     foam = sample_foam(foams, uv_scales, grid, vertex_distance, rx, rz)
     return np.stack([foam, rx, rz, np.sqrt(ex * ex + ez * ez)], axis=1).astype(np.float32)
+
+
+def band_rows(n, tiles, cus):
+    """Rows per band of k_foam_update's row walk for a launch of `tiles` tiles on `cus` compute units: the host's rule (foam_band_rows,
+    ocean_consumers.hip), mirrored ONLY so that a test can assert that its shapes reach the band sizes it names.  Never an expected value."""
+    rows = 32
+    while rows > 4 and tiles * n * n / 256.0 / rows < 4.0 * cus:
+        rows //= 2
+    return min(rows, n)

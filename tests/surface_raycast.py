@@ -26,7 +26,7 @@ class Surface:
         hsum = F(0.0)
         for a in amps:
             hsum = F(hsum + F(a))
-        self.hmax = F(F(1.001) * hsum)
+        self.hmax = np.fmax(F(F(1.001) * hsum), F(1e-3))               # the header's 1 mm floor (a flat sea has amp = FLT_MIN)
 
     def height(self, qx, qz, chunk=1 << 20):
         """H(x, z): out_pos.y of ocean_query_surface, for arrays of points."""
@@ -157,3 +157,53 @@ def raycast_surface(surf, rays, max_distance, steps=0, refine=0, detail=False):
     if detail:
         return out_hit, out_nrm, closest
     return out_hit, out_nrm
+
+
+# ---- a flat sea: phillips_const = 0, so every height is 0 and the amplitude is FLT_MIN (the reference's min/max quirk) ----------------------
+def flat_sea_rays(count=4099, seed=0):
+    """Downward rays onto calm water: origins 1 .. 30 m up, 5 .. 90 degrees below the horizon, any heading, direction lengths 0.5 .. 3."""
+    rng = np.random.default_rng(seed)
+    xz = rng.uniform(-400.0, 400.0, (count, 2))
+    y = rng.uniform(1.0, 30.0, count)
+    pitch = rng.uniform(np.radians(5.0), np.radians(90.0), count)
+    yaw = rng.uniform(0.0, 2.0 * np.pi, count)
+    d = np.stack([np.cos(pitch) * np.sin(yaw), -np.sin(pitch), np.cos(pitch) * np.cos(yaw)], axis=1) * rng.uniform(0.5, 3.0, (count, 1))
+    return np.concatenate([xz[:, :1], y[:, None], xz[:, 1:], d], axis=1).astype(np.float32)
+
+
+def check_flat_sea(rays, hit, nrm, tag=""):
+    """Every ray of flat_sea_rays meets the plane y = 0.  f(t) = o.y + t * d.y is linear, so the secant point is its zero up to rounding:
+    each of f(a), f(b) and the final p(t).y carries one rounding of t * d.y and one of the sum, at most 1 ulp(o.y) each, and t its own
+    half ulp -- 4 ulp(o.y) for the gap and 4 * 2^-23 for t against o.y / -d.y bound them with room.  Returns the two worst figures."""
+    o, d, _ = unit_rays(rays)
+    assert np.all(hit[:, 3] >= 0.0), (tag, "misses / under", int((hit[:, 3] == -1.0).sum()), int((hit[:, 3] == -2.0).sum()))
+    assert np.all(hit[:, 1] == 0.0), tag
+    assert np.array_equal(nrm[:, :3], np.tile(np.array([0.0, 1.0, 0.0], np.float32), (len(rays), 1))), tag
+    gap_ulps = float((np.abs(nrm[:, 3]) / np.spacing(o[:, 1])).max())
+    t_err = float(np.abs(hit[:, 3].astype(np.float64) * -d[:, 1].astype(np.float64) / o[:, 1].astype(np.float64) - 1.0).max())
+    assert gap_ulps <= 4.0, (tag, gap_ulps)
+    assert t_err <= 4.0 * 2.0 ** -23, (tag, t_err)
+    return gap_ulps, t_err
+
+
+# Six rays at the surface of a flat sea, 40 m of reach: (ray, status), status 0 = a hit at t = 5e-4, 1 = a miss, 2 = under water.
+NEAR_SURFACE = [
+    ([3.0, 5e-4, -2.0, 0.0, -1.0, 0.0], 0),             # half a millimetre up, pointing down
+    ([3.0, 0.0, -2.0, 0.0, -1.0, 0.0], 2),              # on the plane: f(0) = 0 counts as wet
+    ([3.0, -5e-4, -2.0, 0.3, -1.0, 0.1], 2),            # inside the slab, under the plane
+    ([3.0, -1e-3, -2.0, 0.0, 1.0, 0.0], 2),             # o.y == -Hmax: below the slab
+    ([3.0, 5e-4, -2.0, 1.0, 0.0, 0.5], 1),              # horizontal above the plane
+    ([3.0, 5e-4, -2.0, 0.2, 1.0, 0.0], 1),              # pointing up
+]
+
+
+def check_near_surface(hit, nrm, tag=""):
+    rays = np.array([r for r, _ in NEAR_SURFACE], np.float32)
+    want = np.array([s for _, s in NEAR_SURFACE])
+    status = np.where(hit[:, 3] >= 0.0, 0, np.where(hit[:, 3] == -2.0, 2, 1))
+    assert np.array_equal(status, want), (tag, status)
+    assert abs(float(hit[0, 3]) / 5e-4 - 1.0) <= 4.0 * 2.0 ** -23 and hit[0, 1] == 0.0, (tag, hit[0])     # as check_flat_sea: f is linear
+    under = want == 2
+    assert np.array_equal(hit[under, :3], np.stack([rays[under, 0], np.zeros(3, np.float32), rays[under, 2]], 1)), tag
+    assert np.array_equal(nrm[under, 3], rays[under, 1]) and np.all(nrm[under, 3] <= 0.0), tag           # the depth: o.y - 0
+    assert np.array_equal(hit[want == 1], np.tile(np.array([0, 0, 0, -1], np.float32), (2, 1))) and not nrm[want == 1].any(), tag

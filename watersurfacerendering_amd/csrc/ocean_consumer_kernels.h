@@ -300,7 +300,7 @@ __global__ void __launch_bounds__(256) k_raycast_surface(const RaycastArgs r)
     float hsum = 0.0f;
 #pragma unroll
     for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) hsum = hsum + amp[c];
-    const float hmax = 1.001f * hsum;
+    const float hmax = fmaxf(1.001f * hsum, 1e-3f);                    // a 1 mm floor: a flat sea (A = FLT_MIN) still gets a slab to bracket
 
     int state = DONE, status = MISS;
     float ox = 0.0f, oy = 0.0f, oz = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f, t0 = 0.0f, t1 = 0.0f;
