@@ -293,6 +293,36 @@ public:
                                reinterpret_cast<float*>(out.data())), "ocean_query_foam");
     }
 
+    // Beyond the reference: buoyancy (ocean_buoyancy_bodies) -- the net force and torque the water of the last ComputeWaves puts on
+    // floating bodies, on the geometry of QuerySurface.  SetHull uploads the hull sample points once, in body space: (local x, y, z, edge
+    // of the cubic cell); it is kept across Prepare and SetTileSize.  Buoyancy takes the bodies' poses, velocities and hull ranges and
+    // gives forces[i] = (F, submerged volume in m^3), torques[i] = (T about the body origin, largest query residual in metres); the
+    // library's density, gravity and drag unless the caller passes its own.
+    void SetHull(const std::vector<vec4>& points)
+    {
+        static_assert(sizeof(vec4) == 16, "hull points are float quadruples");
+        if (m_Pending) Wait();
+        Check(ocean_set_hull(m_Ctx, reinterpret_cast<const float*>(points.data()), (uint32_t)points.size()), "ocean_set_hull");
+    }
+    void Buoyancy(const std::vector<ocean_body>& bodies, std::vector<vec4>& forces, std::vector<vec4>& torques,
+                  const ocean_buoyancy* paramsOrNull = nullptr, uint32_t iterations = 8)
+    {
+        ocean_surface s{};
+        s.first_tile = 0; s.cascades = 1;
+        s.grid_size = ocean_tile_size(m_Ctx);
+        s.vertex_distance = s_kDefaultTileLength / (float)s_kDefaultTileSize;
+        s.choppy = GetDisplacementLambda();
+        s.iterations = iterations;
+        s.uv_scales[0] = 1.0f;
+        ocean_buoyancy p;
+        ocean_default_buoyancy(&p);
+        if (paramsOrNull) p = *paramsOrNull;
+        forces.resize(bodies.size());
+        torques.resize(bodies.size());
+        Check(ocean_buoyancy_bodies(m_Ctx, &s, &p, bodies.data(), (uint32_t)bodies.size(),
+                                    reinterpret_cast<float*>(forces.data()), reinterpret_cast<float*>(torques.data())), "ocean_buoyancy_bodies");
+    }
+
 private:
     bool Pin(int i)
     {

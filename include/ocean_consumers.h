@@ -201,6 +201,66 @@ int ocean_device_foam(ocean_t* ctx, void** d_foam /* [tiles][N][N] */);
 int ocean_query_foam(ocean_t* ctx, const ocean_surface* s, const float* xz, uint32_t points, float* out /* 4 * points */);
 int ocean_query_foam_device(ocean_t* ctx, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out);
 
+/* ---- buoyancy: net force and torque on floating bodies, reduced on the device ------------------------------------------
+ * What most callers do with the surface query: push a few hull points per boat through it, read every point back and add up
+ * "if (depth > 0) apply_force(...)" on the host.  Here the hull is uploaded once, in body space, and a call takes bodies in and
+ * gives one force and one torque per body out.
+ * Hull     ocean_set_hull uploads `count` sample points (local x, y, z, edge e) into a device buffer the context owns.  A point is
+ *          a cubic cell of edge e centred at the local position: a voxelised hull, or a buoy as one cell.  Checked on the host: every
+ *          e > 0 and finite, every position finite, otherwise OCEAN_E_INVALID and the old hull stays.  In-flight work is drained
+ *          before the buffer is replaced.  The hull does not depend on the maps: it survives ocean_prepare and ocean_set_tile_size
+ *          and is freed by ocean_destroy.  count == 0 drops the hull.
+ * Body     ocean_body, 16 words.  Its points are [first_point, first_point + points) of the hull; ranges of different bodies may
+ *          overlap or coincide (instancing).  The quaternion (x, y, z, w) is used as given, not normalised.  Torques are about `pos`.
+ * The water under a hull point is what ocean_query_surface answers for the same ocean_surface: the same K Newton steps.  For hull
+ * point l = (lx, ly, lz), edge e, of a body with quaternion q, in fp32 throughout, no contraction, in exactly this order (the test
+ * suite repeats it step for step; cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x)):
+ *   Arm         t = 2.0f * cross(q.xyz, l) (each component);  a = (l + q.w * t) + cross(q.xyz, t);  p = pos + a
+ *   Water       H = out_pos.y and res = out_nrm.w of ocean_query_surface at (p.x, p.z)
+ *   Submersion  s = fminf(fmaxf((H - p.y) / e + 0.5f, 0.0f), 1.0f);  v = s * ((e * e) * e)
+ *   Force       u = vel + cross(omega, a);  weight = density * gravity (one float product on the host);  dv = drag * v
+ *               f = ((-dv) * u.x,  weight * v - dv * u.y,  (-dv) * u.z);   tq = cross(a, f)
+ *               Archimedes straight up, and linear drag against the point's own velocity in proportion to its submerged volume.
+ *   Reduction   eight channels: f.x, f.y, f.z, tq.x, tq.y, tq.z, v are summed, res is combined with fmaxf from 0.0f.  The order is
+ *               fixed: slot k = 0 .. 63 takes the body's points k, k + 64, k + 128, ... in that order, slot = slot + term from +0.0f
+ *               (an empty slot stays +0.0f); then for off = 32, 16, 8, 4, 2, 1 in turn slot[k] = slot[k] + slot[k + off] for k < off
+ *               (fmaxf(slot[k], slot[k + off]) for res).  The result is slot[0].
+ *   Output      out_force[b] = (F.x, F.y, F.z, V), V the submerged volume in m^3;  out_torque[b] = (T.x, T.y, T.z, largest res):
+ *               the residual tells when a body sits on a fold, as out_nrm.w does for the query.  A body without points: all +0.0f.
+ * Not covered: the water's own particle velocity (drag is against still water); slamming and added mass; integrating the bodies --
+ * that is the caller's physics engine's job, which is why the call returns forces and not new poses.
+ * Both calls read the most recently enqueued frame (caller-bound or imported output where it is) and are stream-ordered behind it
+ * like ocean_query_surface; the fault rule of ocean.h holds unchanged.  ocean_buoyancy_bodies: host arrays bodies[count],
+ * out_force[4*count], out_torque[4*count], staged through the context's staging buffer; returns when the results are there.  A body
+ * whose [first_point, first_point + points) leaves the hull is rejected (OCEAN_E_INVALID) before anything is launched.
+ * ocean_buoyancy_bodies_device: the same arrays in device memory of the context's device (16-byte aligned); enqueued behind the
+ * most recent frame on its stream (ocean_stream), returns at once.  The host cannot see those bodies, so the kernel clamps each
+ * range to the hull: first = min(first_point, hull points), and the points summed are first .. first + min(points, hull points -
+ * first) - 1 (none where first_point is at or past the end).  A body never reads outside the hull buffer.
+ * Errors: OCEAN_E_NOT_READY without Prepare or frame, or without a hull; OCEAN_E_INVALID for a NULL context, surface or
+ * parameters, the invalid ocean_surface cases of ocean_query_surface, a density, gravity or drag that is negative or not finite,
+ * a NULL array with count > 0, a hull point that fails the check above.  count == 0 (bodies) does nothing and returns OCEAN_OK
+ * before the pointers are looked at.  (An addition to ABI version 5: nothing of the existing entry points or structures changes.) */
+typedef struct ocean_body {            /* 16 words, 64 bytes */
+    float    pos[3];                   /* world position of the body origin (torques are about it: put it at the centre of mass) */
+    float    quat[4];                  /* x, y, z, w; used as given, not normalised */
+    float    vel[3], omega[3];         /* linear / angular velocity, world frame */
+    uint32_t first_point, points;      /* this body's range of the uploaded hull; ranges may overlap (instancing) */
+    uint32_t reserved;                 /* 0 */
+} ocean_body;
+typedef struct ocean_buoyancy {
+    float density;                     /* of the water, kg/m^3                                       default 1025  */
+    float gravity;                     /* m/s^2                                                      default 9.81  */
+    float drag;                        /* N per (m/s) per m^3 of submerged volume                    default 1000  */
+} ocean_buoyancy;                      /* all finite and >= 0 */
+
+void ocean_default_buoyancy(ocean_buoyancy* b);
+int ocean_set_hull(ocean_t* ctx, const float* points /* 4 * count: local x, y, z, edge e */, uint32_t count);
+int ocean_buoyancy_bodies(ocean_t* ctx, const ocean_surface* s, const ocean_buoyancy* b, const ocean_body* bodies, uint32_t count,
+                          float* out_force /* 4 * count */, float* out_torque /* 4 * count */);
+int ocean_buoyancy_bodies_device(ocean_t* ctx, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
+                                 void* d_out_force, void* d_out_torque);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,11 @@ import numpy as np
 from . import _abi
 from ._abi import OceanError, Params, build  # noqa: F401
 
-__all__ = ["WSTessendorf", "OceanBatch", "OceanError", "build", "host_register", "host_unregister", "comm_unique_id"]
+__all__ = ["WSTessendorf", "OceanBatch", "OceanError", "build", "host_register", "host_unregister", "comm_unique_id", "BODY_DTYPE"]
+
+#: struct ocean_body (include/ocean_consumers.h) as a numpy record: what OceanBatch.buoyancy takes
+BODY_DTYPE = np.dtype([("pos", np.float32, 3), ("quat", np.float32, 4), ("vel", np.float32, 3), ("omega", np.float32, 3),
+                       ("first_point", np.uint32), ("points", np.uint32), ("reserved", np.uint32)])
 
 
 def _is_pow2(n: int) -> bool:
@@ -374,6 +378,60 @@ class OceanBatch:
         _abi.check(self._L.ocean_query_foam_device(self._h, C.byref(s), C.c_void_p(d_xz), int(points), C.c_void_p(d_out)),
                    "ocean_query_foam_device")
 
+    # -- buoyancy (include/ocean_consumers.h: ocean_set_hull, ocean_buoyancy_bodies) ---------------------------------------
+    def set_hull(self, points):
+        """Upload the hull sample points [count, 4] (local x, y, z, edge of the cubic cell) the bodies of buoyancy() refer to
+        (ocean_set_hull); None or an empty array drops the hull.  Kept across prepare() and set_tile_size()."""
+        p = np.zeros((0, 4), np.float32) if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        _abi.check(self._L.ocean_set_hull(self._h, p.ctypes.data_as(C.c_void_p) if len(p) else None, len(p)), "ocean_set_hull")
+
+    @staticmethod
+    def buoyancy_params(**params) -> "_abi.Buoyancy":
+        """struct ocean_buoyancy with the library's defaults (ocean_default_buoyancy), patched by density / gravity / drag."""
+        p = _abi.Buoyancy()
+        _abi.lib().ocean_default_buoyancy(C.byref(p))
+        for k, v in params.items():
+            if k not in ("density", "gravity", "drag"):
+                raise TypeError(f"unknown buoyancy parameter {k!r}")
+            setattr(p, k, float(v))
+        return p
+
+    @staticmethod
+    def _body_words(bodies) -> np.ndarray:
+        """[count, 16] uint32 words of ocean_body from a BODY_DTYPE record array, or from [count, 16] 4-byte words taken as they are."""
+        b = np.asarray(bodies)
+        if b.dtype == BODY_DTYPE:
+            return np.ascontiguousarray(b).reshape(-1).view(np.uint32).reshape(-1, 16)
+        if b.dtype.itemsize != 4 or b.dtype.kind not in "fiu" or b.ndim != 2 or b.shape[1] != 16:
+            raise ValueError("bodies: a BODY_DTYPE record array or [count, 16] 4-byte words")
+        return np.ascontiguousarray(b).view(np.uint32)
+
+    def buoyancy(self, bodies, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                 vertex_distance: Optional[float] = None, choppy: float = -1.0, iterations: int = 8, **params):
+        """Net buoyancy and drag on floating bodies (ocean_buoyancy_bodies) on the most recent frame, over the hull of set_hull():
+        bodies is a BODY_DTYPE record array (or [count, 16] words), params patch density / gravity / drag.  Returns (force, torque),
+        each (count, 4) float32: force = (F.x, F.y, F.z, submerged volume in m^3), torque = (T about the body origin, the largest
+        query residual in metres).  The surface is query_surface's, same defaults."""
+        w = self._body_words(bodies)
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        p = self.buoyancy_params(**params)
+        force = np.empty((w.shape[0], 4), dtype=np.float32)
+        torque = np.empty_like(force)
+        _abi.check(self._L.ocean_buoyancy_bodies(self._h, C.byref(s), C.byref(p), w.ctypes.data_as(C.c_void_p), w.shape[0],
+                                                 force.ctypes.data_as(C.c_void_p), torque.ctypes.data_as(C.c_void_p)), "ocean_buoyancy_bodies")
+        return force, torque
+
+    def buoyancy_device(self, d_bodies: int, count: int, d_force: int, d_torque: int, first_tile: int = 0, uv_scales=(1.0,),
+                        grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0,
+                        iterations: int = 8, **params):
+        """buoyancy on device arrays of the context's device (ocean_buoyancy_bodies_device; e.g. torch tensors' data_ptr(), 16-byte
+        aligned): d_bodies [count][16] words, d_force / d_torque [count][4] float32.  A range that leaves the hull is clamped to it.
+        Enqueued on the frame's stream (`stream`); returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        p = self.buoyancy_params(**params)
+        _abi.check(self._L.ocean_buoyancy_bodies_device(self._h, C.byref(s), C.byref(p), C.c_void_p(d_bodies), int(count),
+                                                        C.c_void_p(d_force), C.c_void_p(d_torque)), "ocean_buoyancy_bodies_device")
+
     def build_mips(self, tile: int = 0):
         """Mip chain of both maps of `tile` (ocean_build_mips: the reference's s_kUseMipMapping path, Texture2D.cpp:228-330):
         returns (disp_levels, nrm_levels), lists of (N >> l, N >> l, 4) float32 arrays for l = 1 .. log2 N."""
@@ -694,3 +752,22 @@ class WSTessendorf:
             out[...] = res.reshape(out.shape)
             res = out
         return res
+
+    # -- beyond the reference: buoyancy (include/WSTessendorf.hpp: SetHull / Buoyancy) ------------------------------------------
+    def SetHull(self, points):
+        """The hull sample points [count, 4] (local x, y, z, edge of the cubic cell) of Buoyancy() (ocean_set_hull); kept across Prepare()."""
+        self._b.set_hull(points)
+
+    def Buoyancy(self, bodies, forces: np.ndarray | None = None, torques: np.ndarray | None = None, iterations: int = 8, **params):
+        """Net force and torque on each floating body (BODY_DTYPE records) from the water of the last ComputeWaves
+        (ocean_buoyancy_bodies), on the geometry of QuerySurface; params patch density / gravity / drag.  Fills forces / torques
+        [bodies, 4] float32 when given, and returns them: (F, submerged volume), (T about the body origin, largest residual)."""
+        f, t = self._b.buoyancy(bodies, grid_size=self._b.tile_size, vertex_distance=self.s_kDefaultTileLength / self.s_kDefaultTileSize,
+                                choppy=self.GetDisplacementLambda(), iterations=iterations, **params)
+        if forces is not None:
+            forces[...] = f.reshape(forces.shape)
+            f = forces
+        if torques is not None:
+            torques[...] = t.reshape(torques.shape)
+            t = torques
+        return f, t

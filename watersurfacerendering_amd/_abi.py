@@ -43,6 +43,7 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_mip_texels", "ocean_build_mips", "ocean_read_mips", "ocean_device_mips",
     "ocean_query_surface", "ocean_query_surface_device", "ocean_raycast_surface", "ocean_raycast_surface_device",
     "ocean_default_foam", "ocean_update_foam", "ocean_reset_foam", "ocean_read_foam", "ocean_device_foam", "ocean_query_foam", "ocean_query_foam_device",
+    "ocean_default_buoyancy", "ocean_set_hull", "ocean_buoyancy_bodies", "ocean_buoyancy_bodies_device",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
     "ocean_read_spectrum", "ocean_read_xi",
@@ -94,6 +95,17 @@ class Raycast(C.Structure):
 class Foam(C.Structure):
     """struct ocean_foam (include/ocean_consumers.h): how the persistent foam is generated, spreads and fades."""
     _fields_ = [("threshold", C.c_float), ("gain", C.c_float), ("lifetime", C.c_float), ("spread", C.c_float), ("cutoff", C.c_float)]
+
+
+class Body(C.Structure):
+    """struct ocean_body (include/ocean_consumers.h): one floating body's pose, velocities and range of the hull; 16 words."""
+    _fields_ = [("pos", C.c_float * 3), ("quat", C.c_float * 4), ("vel", C.c_float * 3), ("omega", C.c_float * 3),
+                ("first_point", C.c_uint32), ("points", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Buoyancy(C.Structure):
+    """struct ocean_buoyancy (include/ocean_consumers.h): water density, gravity and the linear drag per submerged volume."""
+    _fields_ = [("density", C.c_float), ("gravity", C.c_float), ("drag", C.c_float)]
 
 
 last_build = ""      # what the most recent build() did, for the caller to log
@@ -239,6 +251,10 @@ def lib() -> C.CDLL:
         "ocean_device_foam": (i32, [P, C.POINTER(P)]),
         "ocean_query_foam": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p]),
         "ocean_query_foam_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p]),
+        "ocean_default_buoyancy": (None, [C.POINTER(Buoyancy)]),
+        "ocean_set_hull": (i32, [P, C.c_void_p, u32]),
+        "ocean_buoyancy_bodies": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_buoyancy_bodies_device": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_set_mode": (i32, [P, i32]),
         "ocean_set_dispersion": (i32, [P, i32, f32]),
         "ocean_set_spectrum_precision": (i32, [P, i32]),

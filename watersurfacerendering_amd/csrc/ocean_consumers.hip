@@ -1,10 +1,11 @@
 // ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
-// cascades, mip chain, surface query, ray cast, persistent foam) and the device memory those calls own.  Their kernels: ocean_consumer_kernels.h,
-// ocean_foam_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy) and the device memory those calls own.  Their kernels:
+// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_buoyancy_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
 #include <cmath>
 
 #include "ocean_ctx.h"
 #include "ocean_foam_kernels.h"     // (includes ocean_consumer_kernels.h)
+#include "ocean_buoyancy_kernels.h"
 
 using namespace ocean;
 
@@ -87,6 +88,7 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     if (!everything) return;
     free_and_null(c->grid_pos); free_and_null(c->grid_nrm); c->grid_capacity = 0;
     free_and_null(c->mips_disp); free_and_null(c->mips_nrm); c->mips_n = 0;
+    free_and_null(c->hull); c->hull_points = 0;
     if (c->consumer_ev) { (void)hipEventDestroy(c->consumer_ev); c->consumer_ev = nullptr; }
     c->consumer_pending = false;
 }
@@ -525,6 +527,92 @@ int ocean_query_foam_device(ocean_t* c, const ocean_surface* s, const void* d_xz
     LastFrame f;
     FoamQueryArgs a{};
     return device_call(c, foam_query_args(c, s, f, a), f, a, launch_foam_query, points, d_xz, d_out, nullptr, 1);
+}
+
+}  // extern "C"
+
+// ---- buoyancy (include/ocean_consumers.h) --------------------------------------------------------------------------------------------------
+// ... of the buoyancy call: the parameters, the surface of the query, then the hull.
+static int buoyancy_args(ocean_ctx* c, const ocean_surface* s, const ocean_buoyancy* p, LastFrame& f, BuoyancyArgs& a)
+{
+    if (!c || !s || !p || !std::isfinite(p->density) || !std::isfinite(p->gravity) || !std::isfinite(p->drag) ||
+        p->density < 0.0f || p->gravity < 0.0f || p->drag < 0.0f)
+        return OCEAN_E_INVALID;
+    OCEAN_TRY(query_args(c, s, f, a.q));
+    if (!c->hull) return OCEAN_E_NOT_READY;
+    a.hull = c->hull;
+    a.hull_points = c->hull_points;
+    a.weight = p->density * p->gravity;
+    a.drag = p->drag;
+    return OCEAN_OK;
+}
+
+static int launch_buoyancy(BuoyancyArgs& a, uint32_t count, const void* d_bodies, void* d_out_force, void* d_out_torque, hipStream_t st)
+{
+    a.bodies = static_cast<const float*>(d_bodies);
+    a.out_force = static_cast<float4*>(d_out_force);
+    a.out_torque = static_cast<float4*>(d_out_torque);
+    a.count = count;
+    const unsigned per_block = BUOYANCY_BODIES_PER_BLOCK;
+    hipLaunchKernelGGL(k_buoyancy_bodies, dim3((unsigned)(((uint64_t)a.count + per_block - 1u) / per_block)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+void ocean_default_buoyancy(ocean_buoyancy* b)
+{
+    if (!b) return;
+    b->density = 1025.0f;
+    b->gravity = 9.81f;
+    b->drag = 1000.0f;
+}
+
+int ocean_set_hull(ocean_t* c, const float* points, uint32_t count)
+{
+    static_assert(sizeof(ocean_body) == 64, "a body is 16 words");
+    if (!c || (count && !points)) return OCEAN_E_INVALID;
+    for (size_t i = 0; i < (size_t)count; ++i) {
+        const float* p = points + 4 * i;
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(p[3]) || !(p[3] > 0.0f)) return OCEAN_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // the new buffer is complete before the old one goes: a failure leaves the old hull
+    float4* fresh = nullptr;
+    if (count) {
+        const size_t bytes = (size_t)count * sizeof(float4), guard = OCEAN_HULL_GUARD * sizeof(float4);
+        HIP_TRY(hipMalloc(&fresh, bytes + guard));
+        hipError_t e = hipMemcpy(fresh, points, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(fresh + count, 0xff, guard);        // all bits set: NaN in every word
+        if (e != hipSuccess) { (void)hipFree(fresh); HIP_TRY(e); }
+    }
+    const int rc = c->hull ? sync_all(c) : OCEAN_OK;      // nothing in flight may still read the old one
+    if (rc) { if (fresh) (void)hipFree(fresh); return rc; }
+    free_and_null(c->hull);
+    c->hull = fresh;
+    c->hull_points = count;
+    return OCEAN_OK;
+}
+
+int ocean_buoyancy_bodies(ocean_t* c, const ocean_surface* s, const ocean_buoyancy* b, const ocean_body* bodies, uint32_t count,
+                          float* out_force, float* out_torque)
+{
+    LastFrame f;
+    BuoyancyArgs a{};
+    const int rc = buoyancy_args(c, s, b, f, a);
+    if (rc == OCEAN_OK && bodies)       // (a NULL array is staged_call's to report)
+        for (uint32_t i = 0; i < count; ++i)
+            if ((uint64_t)bodies[i].first_point + bodies[i].points > a.hull_points) return OCEAN_E_INVALID;
+    return staged_call(c, rc, f, a, launch_buoyancy, count, reinterpret_cast<const float*>(bodies), 16, out_force, out_torque, 2);
+}
+
+int ocean_buoyancy_bodies_device(ocean_t* c, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
+                                 void* d_out_force, void* d_out_torque)
+{
+    LastFrame f;
+    BuoyancyArgs a{};
+    return device_call(c, buoyancy_args(c, s, b, f, a), f, a, launch_buoyancy, count, d_bodies, d_out_force, d_out_torque, 2);
 }
 
 }  // extern "C"

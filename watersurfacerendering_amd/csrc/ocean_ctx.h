@@ -15,6 +15,7 @@
 
 constexpr int MAXD = 8;     // maximum pipeline depth (independent frame chains)
 constexpr int OCEAN_MAX_LAUNCHES = 3;   // launches per frame: at most three (ocean_launch.h)
+constexpr uint32_t OCEAN_HULL_GUARD = 64;   // NaN points allocated behind the hull of ocean_set_hull (ocean_ctx::hull)
 
 // ---- launch and store-policy heuristics: every measured constant in ONE place -----------------------------------------
 // The rules are written in quantities of the device and of the launch -- compute units x resident workgroups per unit (asked of the runtime:
@@ -198,6 +199,11 @@ struct ocean_ctx {
     bool foam_ready = false;        // an update has been enqueued since the last ocean_prepare
     float* foam_lambda = nullptr;   // [tiles] lambdas of a FULL7 frame whose tiles differ (uploaded when they change: foam_lambda_host)
     std::vector<float> foam_lambda_host;
+    // Hull sample points of ocean_buoyancy_bodies (ocean_set_hull).  The allocation is hull_points + OCEAN_HULL_GUARD float4: [hull_points]
+    // (x, y, z, edge) followed by OCEAN_HULL_GUARD points of NaN (1 KB) that no body may reach -- a range check gone wrong poisons its body's
+    // sums instead of reading stray memory.  Independent of the maps: kept across ocean_prepare / ocean_set_tile_size, freed by ocean_destroy.
+    float4* hull = nullptr;
+    uint32_t hull_points = 0;
     unsigned long long* stamps = nullptr;   // diagnostic builds only
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
