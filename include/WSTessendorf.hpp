@@ -72,11 +72,16 @@ public:
     using Normal       = vec4;
     static_assert(sizeof(vec4) == 16, "maps are RGBA32F");
 
+    // withVelocity (beyond the reference): the context carries a second tile, the derivative twin of the model's own
+    // (ocean_set_velocity_twin), which QueryVelocity and BuoyancyFlow read.  It costs one more tile per frame; everything the
+    // reference's methods return is the model's own tile, unchanged.
     explicit WSTessendorf(uint32_t tileSize = s_kDefaultTileSize, float tileLength = s_kDefaultTileLength,
-                          int device = 0)
+                          int device = 0, bool withVelocity = false)
+        : m_Velocity(withVelocity)
     {
         if (tileSize == 0 || (tileSize & (tileSize - 1))) tileSize = s_kDefaultTileSize;
-        Check(ocean_create(&m_Ctx, tileSize, 1, device), "ocean_create");
+        Check(ocean_create(&m_Ctx, tileSize, withVelocity ? 2 : 1, device), "ocean_create");
+        if (withVelocity) Check(ocean_set_velocity_twin(m_Ctx, 1, 0), "ocean_set_velocity_twin");
         ocean_default_params(&m_Params);
         m_Params.tile_length = tileLength;
         Push();
@@ -94,8 +99,14 @@ public:
     void Prepare(uint64_t seed, const float* gaussRandomOrNull = nullptr)
     {
         if (m_Pending) Wait();
-        Check(ocean_prepare(m_Ctx, seed, gaussRandomOrNull), "ocean_prepare");
         const size_t n = ocean_tile_size(m_Ctx);
+        std::vector<float> both;                    // (the twin's part of injected draws is ignored: the model's own, twice)
+        if (m_Velocity && gaussRandomOrNull) {
+            both.assign(gaussRandomOrNull, gaussRandomOrNull + 2 * n * n);
+            both.insert(both.end(), gaussRandomOrNull, gaussRandomOrNull + 2 * n * n);
+            gaussRandomOrNull = both.data();
+        }
+        Check(ocean_prepare(m_Ctx, seed, gaussRandomOrNull), "ocean_prepare");
         Unpin();
         m_Front = 0;
         m_Displacements[1].clear(); m_Normals[1].clear();                      // the back pair exists only once ComputeWavesAsync is used
@@ -110,14 +121,21 @@ public:
     float ComputeWaves(float time)
     {
         if (m_Pending) Wait();
-        float amp = 0.f;
-        // synthesis + both maps into the host vectors, one blocking call: the normal map's copy runs beside the displacement pass
-        // (ocean_compute_waves_read; the same maps as ocean_compute_waves + ocean_read_maps)
-        Check(ocean_compute_waves_read(m_Ctx, time, &amp, reinterpret_cast<float*>(m_Displacements[m_Front].data()),
-                                       reinterpret_cast<float*>(m_Normals[m_Front].data())), "ocean_compute_waves_read");
+        float amp[2] = { 0.f, 0.f };                // (per tile: the model's own, then its twin's where there is one)
+        if (m_Velocity) {
+            // the combined call reads every tile out; only the model's own tile goes to the host vectors
+            Check(ocean_compute_waves(m_Ctx, time, amp), "ocean_compute_waves");
+            Check(ocean_read_maps(m_Ctx, 0, 1, reinterpret_cast<float*>(m_Displacements[m_Front].data()),
+                                  reinterpret_cast<float*>(m_Normals[m_Front].data())), "ocean_read_maps");
+        } else {
+            // synthesis + both maps into the host vectors, one blocking call: the normal map's copy runs beside the displacement pass
+            // (ocean_compute_waves_read; the same maps as ocean_compute_waves + ocean_read_maps)
+            Check(ocean_compute_waves_read(m_Ctx, time, amp, reinterpret_cast<float*>(m_Displacements[m_Front].data()),
+                                           reinterpret_cast<float*>(m_Normals[m_Front].data())), "ocean_compute_waves_read");
+        }
         float a;
         Check(ocean_get_heights(m_Ctx, 0, &a, &m_MinHeight, &m_MaxHeight), "ocean_get_heights");
-        return amp;
+        return amp[0];
     }
 
     // Opt-in non-blocking pair, beyond the reference -- whose own note on its DOUBLE_BUFFERED switch says "should be on dedicated
@@ -141,11 +159,11 @@ public:
         Check(ocean_compute_waves_async(m_Ctx, time), "ocean_compute_waves_async");
         Check(ocean_read_maps_async(m_Ctx, 0, 1, reinterpret_cast<float*>(m_Displacements[back].data()),
                                     reinterpret_cast<float*>(m_Normals[back].data())), "ocean_read_maps_async");
-        float amp = 0.f, a;
-        Check(ocean_wait_frame(m_Ctx, &amp), "ocean_wait_frame");
+        float amp[2] = { 0.f, 0.f }, a;             // (per tile, as in ComputeWaves)
+        Check(ocean_wait_frame(m_Ctx, amp), "ocean_wait_frame");
         Check(ocean_get_heights(m_Ctx, 0, &a, &m_PendingMin, &m_PendingMax), "ocean_get_heights");
         m_Pending = true;
-        return amp;
+        return amp[0];
     }
     void Wait()
     {
@@ -323,6 +341,42 @@ public:
                                     reinterpret_cast<float*>(forces.data()), reinterpret_cast<float*>(torques.data())), "ocean_buoyancy_bodies");
     }
 
+    // Beyond the reference: water velocity (ocean_query_velocity, ocean_buoyancy_bodies_flow), for a model constructed withVelocity.
+    // QueryVelocity: positions[i] exactly as QuerySurface, velocities[i] = (V.x, V.y, V.z in m/s, residual in metres) of the water
+    // particle at the point.  BuoyancyFlow: Buoyancy with the drag taken against that velocity under every hull point.
+    void QueryVelocity(const std::vector<vec2>& xz, std::vector<vec4>& positions, std::vector<vec4>& velocities, uint32_t iterations = 8)
+    {
+        ocean_surface s{};
+        s.first_tile = 0; s.cascades = 1;
+        s.grid_size = ocean_tile_size(m_Ctx);
+        s.vertex_distance = s_kDefaultTileLength / (float)s_kDefaultTileSize;
+        s.choppy = GetDisplacementLambda();
+        s.iterations = iterations;
+        s.uv_scales[0] = 1.0f;
+        positions.resize(xz.size());
+        velocities.resize(xz.size());
+        Check(ocean_query_velocity(m_Ctx, &s, reinterpret_cast<const float*>(xz.data()), (uint32_t)xz.size(),
+                                   reinterpret_cast<float*>(positions.data()), reinterpret_cast<float*>(velocities.data())), "ocean_query_velocity");
+    }
+    void BuoyancyFlow(const std::vector<ocean_body>& bodies, std::vector<vec4>& forces, std::vector<vec4>& torques,
+                      const ocean_buoyancy* paramsOrNull = nullptr, uint32_t iterations = 8)
+    {
+        ocean_surface s{};
+        s.first_tile = 0; s.cascades = 1;
+        s.grid_size = ocean_tile_size(m_Ctx);
+        s.vertex_distance = s_kDefaultTileLength / (float)s_kDefaultTileSize;
+        s.choppy = GetDisplacementLambda();
+        s.iterations = iterations;
+        s.uv_scales[0] = 1.0f;
+        ocean_buoyancy p;
+        ocean_default_buoyancy(&p);
+        if (paramsOrNull) p = *paramsOrNull;
+        forces.resize(bodies.size());
+        torques.resize(bodies.size());
+        Check(ocean_buoyancy_bodies_flow(m_Ctx, &s, &p, bodies.data(), (uint32_t)bodies.size(),
+                                         reinterpret_cast<float*>(forces.data()), reinterpret_cast<float*>(torques.data())), "ocean_buoyancy_bodies_flow");
+    }
+
 private:
     bool Pin(int i)
     {
@@ -364,6 +418,7 @@ private:
     float m_MaxHeight{ 1.0f };
     uint64_t m_PrepareCount{ 0 };
     bool m_Pinned[2]{ false, false };
+    bool m_Velocity{ false };                         // the context has a second tile: the derivative twin of the model's own
 };
 
 #endif  // WS_TESSENDORF_ADAPTOR_HPP_

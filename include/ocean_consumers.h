@@ -227,8 +227,8 @@ int ocean_query_foam_device(ocean_t* ctx, const ocean_surface* s, const void* d_
  *               (fmaxf(slot[k], slot[k + off]) for res).  The result is slot[0].
  *   Output      out_force[b] = (F.x, F.y, F.z, V), V the submerged volume in m^3;  out_torque[b] = (T.x, T.y, T.z, largest res):
  *               the residual tells when a body sits on a fold, as out_nrm.w does for the query.  A body without points: all +0.0f.
- * Not covered: the water's own particle velocity (drag is against still water); slamming and added mass; integrating the bodies --
- * that is the caller's physics engine's job, which is why the call returns forces and not new poses.
+ * Not covered: slamming and added mass; integrating the bodies -- that is the caller's physics engine's job, which is why the call
+ * returns forces and not new poses.  (Drag here is against still water; ocean_buoyancy_bodies_flow, below, takes it against the moving water.)
  * Both calls read the most recently enqueued frame (caller-bound or imported output where it is) and are stream-ordered behind it
  * like ocean_query_surface; the fault rule of ocean.h holds unchanged.  ocean_buoyancy_bodies: host arrays bodies[count],
  * out_force[4*count], out_torque[4*count], staged through the context's staging buffer; returns when the results are there.  A body
@@ -260,6 +260,55 @@ int ocean_buoyancy_bodies(ocean_t* ctx, const ocean_surface* s, const ocean_buoy
                           float* out_force /* 4 * count */, float* out_torque /* 4 * count */);
 int ocean_buoyancy_bodies_device(ocean_t* ctx, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
                                  void* d_out_force, void* d_out_torque);
+
+/* ---- water velocity: derivative twin tiles, a velocity query, drag against the moving water ------------------------------
+ * The animated spectrum is real per bin, h~(k, t) = 2 Re(h0(k) e^{i w t}), so its time derivative is 2 Re(i w h0(k) e^{i w t}): the
+ * same expression for the spectrum h0' = i w h0 = (-w h0.im, w h0.re).  Everything behind the spectrum is linear in it, so a tile
+ * prepared with h0' and run through the unchanged frame pipeline writes maps that are the time derivative of its source tile's
+ * maps.  Such a tile is a twin.  It costs one more tile per frame and is opt-in; no frame kernel knows about it.
+ * Twin tiles   ocean_set_velocity_twin makes `tile` the twin of `source` (same batch) from the next ocean_prepare on; source =
+ *          OCEAN_NO_SOURCE makes it an ordinary tile again.  Host state only, like ocean_set_params, but it drains in-flight work
+ *          and leaves the context not prepared: frames and consumers return OCEAN_E_NOT_READY until ocean_prepare.  A source has at
+ *          most one twin and twins of twins are rejected: OCEAN_E_INVALID for a tile (or source) outside the batch, tile == source,
+ *          a source that is itself a twin, a tile that is some twin's source, a source that already has another twin.  The table
+ *          survives ocean_prepare and ocean_set_tile_size.  ocean_velocity_twin reads it (OCEAN_NO_SOURCE for an ordinary tile).
+ *          A twin has no parameters of its own: Prepare and the frames read its source's ocean_params (tile length, animation
+ *          period, ... and lambda on every frame) and its source's time offset (ocean_set_time_offsets), so k and omega are its
+ *          source's.  ocean_set_params / ocean_set_lambda with a twin's explicit index return OCEAN_E_INVALID (OCEAN_ALL_TILES
+ *          behaves as always); ocean_get_params(twin) returns the source's.  Prepare then overwrites every texel of the twin's
+ *          spectrum: h0[twin] = (-(w * h0[src].y), w * h0[src].x), w = omega[src] (fp32, one multiply per component), and copies
+ *          the source's gaussian draws into the twin's slot (injected draws for a twin are ignored).
+ *          A twin's maps, in every mode: disp = (lambda dDx/dt, (dh/dt) / A', lambda dDz/dt, the mode's w slot evaluated for the
+ *          derivative spectrum), A' = max |dh/dt| from the twin's own height keys (ocean_get_heights(twin); the FLT_MIN floor of a
+ *          flat sea as for any tile); nrm = the time derivatives of the four normal-map channels.  A twin's disp.w and its foam
+ *          state mean nothing.
+ * Velocity query  ocean_query_velocity: the velocity of the water particle that sits at world point q at the frame's time, dP/dt at
+ *          a fixed rest point.  The cascade set of `s` is made of source tiles; their twins must be consecutive ascending tiles
+ *          v, v+1, ..., v+cascades-1 in cascade order (below or above the sources).  fp32 throughout, no contraction, in this order:
+ *            r = the K Newton steps of ocean_query_surface at q;  (u, v) = the uv of r as in that query;  V = (0.0f, 0.0f, 0.0f)
+ *            for c in cascade order:  d' = sample of twin c's displacement map at (u, v) * uv_scales[c] (LINEAR, REPEAT)
+ *                                     V.x = V.x + d'.x;  V.y = V.y + d'.y * A'_c;  V.z = V.z + d'.z
+ *            out_pos = exactly ocean_query_surface's out_pos at q;   out_vel = (V.x, V.y, V.z, |P(r).xz - q|)
+ *          Bilinear sampling is linear, so it commutes with the derivative.  Host / device forms, staging, stream order and the
+ *          fault rule as ocean_query_surface / _device.  Errors as ocean_query_surface, and: OCEAN_E_NOT_READY for a set of which
+ *          no tile has a twin; OCEAN_E_INVALID for a set only partly twinned or with twins that are not consecutive.
+ * Flow buoyancy   ocean_buoyancy_bodies_flow / _device: ocean_buoyancy_bodies / _device with the drag taken against the water.  V as
+ *          above at the hull point's (p.x, p.z), from the rest point that gave H (no second Newton solve), and
+ *            u = ((vel.x + (om.y*a.z - om.z*a.y)) - V.x,  (vel.y + (om.z*a.x - om.x*a.z)) - V.y,  (vel.z + (om.x*a.y - om.y*a.x)) - V.z)
+ *          in place of the point's own velocity; everything else -- the reduction order, the outputs, the clamping of body ranges in
+ *          the device form, the errors -- is the text above unchanged.  Twin requirements and errors as ocean_query_velocity.
+ * (An addition to ABI version 5: nothing of the existing entry points or structures changes.)                            */
+#define OCEAN_NO_SOURCE 0xffffffffu
+int ocean_set_velocity_twin(ocean_t* ctx, uint32_t tile, uint32_t source /* or OCEAN_NO_SOURCE */);
+int ocean_velocity_twin(const ocean_t* ctx, uint32_t tile, uint32_t* source);   /* OCEAN_NO_SOURCE for an ordinary tile */
+int ocean_query_velocity(ocean_t* ctx, const ocean_surface* s, const float* xz, uint32_t points,
+                         float* out_pos /* 4 * points */, float* out_vel /* 4 * points */);
+int ocean_query_velocity_device(ocean_t* ctx, const ocean_surface* s, const void* d_xz, uint32_t points,
+                                void* d_out_pos, void* d_out_vel);
+int ocean_buoyancy_bodies_flow(ocean_t* ctx, const ocean_surface* s, const ocean_buoyancy* b, const ocean_body* bodies, uint32_t count,
+                               float* out_force /* 4 * count */, float* out_torque /* 4 * count */);
+int ocean_buoyancy_bodies_flow_device(ocean_t* ctx, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
+                                      void* d_out_force, void* d_out_torque);
 
 #ifdef __cplusplus
 }

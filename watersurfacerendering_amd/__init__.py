@@ -48,6 +48,7 @@ class OceanBatch:
         _abi.check(self._L.ocean_create(C.byref(self._h), tile_size, tiles, device), "ocean_create")
         self.tiles = tiles
         self.device = device
+        self._twins = {}       # twin -> source, as ocean_set_velocity_twin accepted them (what set_params(ALL_TILES) skips)
 
     # -- lifetime ---------------------------------------------------------------
     def close(self):
@@ -73,7 +74,7 @@ class OceanBatch:
 
     def set_params(self, tile: int = _abi.OCEAN_ALL_TILES, **kw):
         """Patch the given fields of one tile, or of EVERY tile (each keeps its other parameters)."""
-        tiles = range(self.tiles) if tile == _abi.OCEAN_ALL_TILES else (tile,)
+        tiles = [i for i in range(self.tiles) if i not in self._twins] if tile == _abi.OCEAN_ALL_TILES else (tile,)   # (a twin has its source's)
         for i in tiles:
             p = self.get_params(i)
             for k, v in kw.items():
@@ -85,6 +86,23 @@ class OceanBatch:
 
     def set_lambda(self, lam: float, tile: int = _abi.OCEAN_ALL_TILES):
         _abi.check(self._L.ocean_set_lambda(self._h, tile, lam), "ocean_set_lambda")
+
+    def set_velocity_twin(self, tile: int, source: Optional[int]):
+        """Make `tile` the derivative twin of `source` from the next prepare() on (ocean_set_velocity_twin): its maps then hold the time
+        derivative of its source's -- what query_velocity and buoyancy_flow read.  source None makes it an ordinary tile again.  The context
+        is not prepared until the next prepare()."""
+        src = _abi.OCEAN_NO_SOURCE if source is None else int(source)
+        _abi.check(self._L.ocean_set_velocity_twin(self._h, int(tile), src), "ocean_set_velocity_twin")
+        if source is None:
+            self._twins.pop(int(tile), None)
+        else:
+            self._twins[int(tile)] = int(source)
+
+    def velocity_twin(self, tile: int) -> Optional[int]:
+        """The source `tile` is the twin of, None for an ordinary tile (ocean_velocity_twin)."""
+        src = C.c_uint32()
+        _abi.check(self._L.ocean_velocity_twin(self._h, int(tile), C.byref(src)), "ocean_velocity_twin")
+        return None if src.value == _abi.OCEAN_NO_SOURCE else int(src.value)
 
     def set_tile_size(self, n: int):
         _abi.check(self._L.ocean_set_tile_size(self._h, n), "ocean_set_tile_size")
@@ -177,6 +195,9 @@ class OceanBatch:
         """Enqueue the D2H copy of the last enqueued frame's maps into caller arrays (pin them with
         host_register for a true asynchronous DMA); valid after synchronize()."""
         count = self.tiles - first if count is None else count
+        need = count * self.tile_size * self.tile_size * 16           # (the library sees raw pointers: it cannot check the arrays)
+        if disp.nbytes < need or nrm.nbytes < need:
+            raise ValueError(f"read_maps_async: {count} tile(s) need {need} bytes per array, got {disp.nbytes} and {nrm.nbytes}")
         _abi.check(self._L.ocean_read_maps_async(self._h, first, count, disp.ctypes.data_as(C.c_void_p),
                                                  nrm.ctypes.data_as(C.c_void_p)), "ocean_read_maps_async")
 
@@ -432,6 +453,52 @@ class OceanBatch:
         _abi.check(self._L.ocean_buoyancy_bodies_device(self._h, C.byref(s), C.byref(p), C.c_void_p(d_bodies), int(count),
                                                         C.c_void_p(d_force), C.c_void_p(d_torque)), "ocean_buoyancy_bodies_device")
 
+    # -- water velocity (include/ocean_consumers.h: ocean_query_velocity, ocean_buoyancy_bodies_flow) ---------------------------
+    def query_velocity(self, xz, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                       vertex_distance: Optional[float] = None, choppy: float = -1.0, iterations: int = 8):
+        """Velocity of the water particle at each world point xz [points, 2] (ocean_query_velocity) on the most recent frame.  The tiles
+        first_tile .. first_tile+len(uv_scales)-1 are the sources; their twins (set_velocity_twin) must be consecutive tiles in the same
+        order.  Returns (pos, vel), each (points, 4) float32: pos exactly as query_surface, vel = (V.x, V.y, V.z in m/s, residual in metres)."""
+        q = np.ascontiguousarray(xz, dtype=np.float32).reshape(-1, 2)
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        pos = np.empty((q.shape[0], 4), dtype=np.float32)
+        vel = np.empty_like(pos)
+        _abi.check(self._L.ocean_query_velocity(self._h, C.byref(s), q.ctypes.data_as(C.c_void_p), q.shape[0],
+                                                pos.ctypes.data_as(C.c_void_p), vel.ctypes.data_as(C.c_void_p)), "ocean_query_velocity")
+        return pos, vel
+
+    def query_velocity_device(self, d_xz: int, points: int, d_pos: int, d_vel: int, first_tile: int = 0, uv_scales=(1.0,),
+                              grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0,
+                              iterations: int = 8):
+        """query_velocity on device arrays of the context's device (ocean_query_velocity_device): d_xz [points][2], d_pos / d_vel
+        [points][4] float32.  Enqueued on the frame's stream (`stream`); returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        _abi.check(self._L.ocean_query_velocity_device(self._h, C.byref(s), C.c_void_p(d_xz), int(points), C.c_void_p(d_pos),
+                                                       C.c_void_p(d_vel)), "ocean_query_velocity_device")
+
+    def buoyancy_flow(self, bodies, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                      vertex_distance: Optional[float] = None, choppy: float = -1.0, iterations: int = 8, **params):
+        """buoyancy() with the drag taken against the moving water (ocean_buoyancy_bodies_flow): the water's velocity under each hull
+        point comes from the twins of the cascade set, as in query_velocity.  Same arguments and results as buoyancy()."""
+        w = self._body_words(bodies)
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        p = self.buoyancy_params(**params)
+        force = np.empty((w.shape[0], 4), dtype=np.float32)
+        torque = np.empty_like(force)
+        _abi.check(self._L.ocean_buoyancy_bodies_flow(self._h, C.byref(s), C.byref(p), w.ctypes.data_as(C.c_void_p), w.shape[0],
+                                                      force.ctypes.data_as(C.c_void_p), torque.ctypes.data_as(C.c_void_p)),
+                   "ocean_buoyancy_bodies_flow")
+        return force, torque
+
+    def buoyancy_flow_device(self, d_bodies: int, count: int, d_force: int, d_torque: int, first_tile: int = 0, uv_scales=(1.0,),
+                             grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0,
+                             iterations: int = 8, **params):
+        """buoyancy_flow on device arrays of the context's device (ocean_buoyancy_bodies_flow_device), as buoyancy_device."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        p = self.buoyancy_params(**params)
+        _abi.check(self._L.ocean_buoyancy_bodies_flow_device(self._h, C.byref(s), C.byref(p), C.c_void_p(d_bodies), int(count),
+                                                             C.c_void_p(d_force), C.c_void_p(d_torque)), "ocean_buoyancy_bodies_flow_device")
+
     def build_mips(self, tile: int = 0):
         """Mip chain of both maps of `tile` (ocean_build_mips: the reference's s_kUseMipMapping path, Texture2D.cpp:228-330):
         returns (disp_levels, nrm_levels), lists of (N >> l, N >> l, 4) float32 arrays for l = 1 .. log2 N."""
@@ -577,10 +644,15 @@ class WSTessendorf:
     s_kDefaultPhillipsConst = 3e-7
     s_kDefaultPhillipsDamping = 0.1
 
-    def __init__(self, tileSize: int = 512, tileLength: float = 1000.0, device: int = 0):
+    def __init__(self, tileSize: int = 512, tileLength: float = 1000.0, device: int = 0, velocity: bool = False):
+        """velocity=True (beyond the reference): the context carries a second tile, the derivative twin of the model's own, which
+        QueryVelocity and BuoyancyFlow read (include/WSTessendorf.hpp: withVelocity).  One more tile per frame."""
         if not _is_pow2(tileSize):
             tileSize = self.s_kDefaultTileSize
-        self._b = OceanBatch(tileSize, 1, device)
+        self._velocity = bool(velocity)
+        self._b = OceanBatch(tileSize, 2 if velocity else 1, device)
+        if velocity:
+            self._b.set_velocity_twin(1, 0)
         self._b.set_params(tile_length=tileLength)
         self._disp = None
         self._nrm = None
@@ -598,6 +670,8 @@ class WSTessendorf:
             seed = (time.time_ns() ^ (self._seed_ctr * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
         if self._pending is not None:
             self.Wait()
+        if self._velocity and xi is not None:       # (the twin's part of injected draws is ignored: the model's own, twice)
+            xi = np.stack([np.asarray(xi, dtype=np.float32).reshape(self._b.tile_size, self._b.tile_size, 2)] * 2)
         self._b.prepare(seed, xi)
         n = self._b.tile_size
         self._disp = np.zeros((n, n, 4), dtype=np.float32)            # .cpp:48-51
@@ -633,7 +707,7 @@ class WSTessendorf:
                 host_register(a)
             self._b.set_frame_tracking(True)
         self._b.compute_waves_async(time)
-        self._b.read_maps_async(self._back[0], self._back[1])
+        self._b.read_maps_async(self._back[0], self._back[1], 0, 1)      # (the model's own tile only: the back pair holds one)
         amp = float(self._b.wait_frame()[0])
         self._pending = self._b.heights(0)
         return amp
@@ -764,6 +838,33 @@ class WSTessendorf:
         [bodies, 4] float32 when given, and returns them: (F, submerged volume), (T about the body origin, largest residual)."""
         f, t = self._b.buoyancy(bodies, grid_size=self._b.tile_size, vertex_distance=self.s_kDefaultTileLength / self.s_kDefaultTileSize,
                                 choppy=self.GetDisplacementLambda(), iterations=iterations, **params)
+        if forces is not None:
+            forces[...] = f.reshape(forces.shape)
+            f = forces
+        if torques is not None:
+            torques[...] = t.reshape(torques.shape)
+            t = torques
+        return f, t
+
+    # -- beyond the reference: water velocity (include/WSTessendorf.hpp: QueryVelocity / BuoyancyFlow), for velocity=True ------------
+    def QueryVelocity(self, xz, positions: np.ndarray | None = None, velocities: np.ndarray | None = None, iterations: int = 8):
+        """Velocity of the water particle at each world point xz [points, 2] (ocean_query_velocity) on the geometry of QuerySurface.
+        Fills positions / velocities [points, 4] float32 when given, and returns them: positions as QuerySurface, velocities =
+        (V.x, V.y, V.z in m/s, residual in metres)."""
+        pos, vel = self._b.query_velocity(xz, grid_size=self._b.tile_size, vertex_distance=self.s_kDefaultTileLength / self.s_kDefaultTileSize,
+                                          choppy=self.GetDisplacementLambda(), iterations=iterations)
+        if positions is not None:
+            positions[...] = pos.reshape(positions.shape)
+            pos = positions
+        if velocities is not None:
+            velocities[...] = vel.reshape(velocities.shape)
+            vel = velocities
+        return pos, vel
+
+    def BuoyancyFlow(self, bodies, forces: np.ndarray | None = None, torques: np.ndarray | None = None, iterations: int = 8, **params):
+        """Buoyancy() with the drag taken against the moving water (ocean_buoyancy_bodies_flow)."""
+        f, t = self._b.buoyancy_flow(bodies, grid_size=self._b.tile_size, vertex_distance=self.s_kDefaultTileLength / self.s_kDefaultTileSize,
+                                     choppy=self.GetDisplacementLambda(), iterations=iterations, **params)
         if forces is not None:
             forces[...] = f.reshape(forces.shape)
             f = forces

@@ -25,6 +25,7 @@ OCEAN_E_UNSUPPORTED = -6
 OCEAN_E_COMM = -7
 OCEAN_COMM_ID_BYTES = 128
 OCEAN_ALL_TILES = 0xFFFFFFFF
+OCEAN_NO_SOURCE = 0xFFFFFFFF       # ocean_set_velocity_twin: an ordinary tile
 OCEAN_MODE_FULL7, OCEAN_MODE_CHOPPY5, OCEAN_MODE_HEIGHT1, OCEAN_MODE_JACOBIAN = 0, 1, 2, 3
 
 #: every symbol the library's three headers declare (tests check the .so exports each one, and that each list equals its header's)
@@ -44,6 +45,8 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_query_surface", "ocean_query_surface_device", "ocean_raycast_surface", "ocean_raycast_surface_device",
     "ocean_default_foam", "ocean_update_foam", "ocean_reset_foam", "ocean_read_foam", "ocean_device_foam", "ocean_query_foam", "ocean_query_foam_device",
     "ocean_default_buoyancy", "ocean_set_hull", "ocean_buoyancy_bodies", "ocean_buoyancy_bodies_device",
+    "ocean_set_velocity_twin", "ocean_velocity_twin", "ocean_query_velocity", "ocean_query_velocity_device",
+    "ocean_buoyancy_bodies_flow", "ocean_buoyancy_bodies_flow_device",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
     "ocean_read_spectrum", "ocean_read_xi",
@@ -255,6 +258,12 @@ def lib() -> C.CDLL:
         "ocean_set_hull": (i32, [P, C.c_void_p, u32]),
         "ocean_buoyancy_bodies": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_buoyancy_bodies_device": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_set_velocity_twin": (i32, [P, u32, u32]),
+        "ocean_velocity_twin": (i32, [P, u32, C.POINTER(u32)]),
+        "ocean_query_velocity": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_query_velocity_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_buoyancy_bodies_flow": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_buoyancy_bodies_flow_device": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_set_mode": (i32, [P, i32]),
         "ocean_set_dispersion": (i32, [P, i32, f32]),
         "ocean_set_spectrum_precision": (i32, [P, i32]),

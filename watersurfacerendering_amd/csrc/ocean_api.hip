@@ -285,6 +285,7 @@ int ocean_create(ocean_t** out, uint32_t tile_size, uint32_t tiles, int device)
     c->n = tile_size; c->tiles = tiles; c->device = device;
     c->cu_count = prop.multiProcessorCount;
     c->params.resize(tiles);
+    c->twin_source.assign(tiles, OCEAN_NO_SOURCE);
     for (auto& p : c->params) ocean_default_params(&p);
     int rc = OCEAN_OK;
     do {
@@ -331,10 +332,50 @@ void ocean_destroy(ocean_t* c)
 
 int ocean_set_lambda(ocean_t* c, uint32_t tile, float lambda);
 
+}  // extern "C"
+
+// The per-tile time offsets as the frames read them: the caller's, a twin with its source's.
+static int upload_time_offsets(ocean_ctx* c)
+{
+    std::vector<float> off(c->tiles);
+    for (uint32_t i = 0; i < c->tiles; ++i) off[i] = c->toff_host[effective_tile(c, i)];
+    HIP_TRY(hipMemcpy(c->toff, off.data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_set_velocity_twin(ocean_t* c, uint32_t tile, uint32_t source)
+{
+    if (!c || tile >= c->tiles) return OCEAN_E_INVALID;
+    if (source != OCEAN_NO_SOURCE) {
+        if (source >= c->tiles || source == tile || c->twin_source[source] != OCEAN_NO_SOURCE) return OCEAN_E_INVALID;     // (no twins of twins)
+        for (uint32_t i = 0; i < c->tiles; ++i) {
+            if (c->twin_source[i] == tile) return OCEAN_E_INVALID;                      // `tile` is some twin's source
+            if (i != tile && c->twin_source[i] == source) return OCEAN_E_INVALID;       // the source has another twin already
+        }
+    }
+    // host state only, but what is prepared and in flight was made for the old table: drained, and nothing runs until the next ocean_prepare
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    c->twin_source[tile] = source;
+    c->prepared = false;
+    c->have_frame = false;
+    c->lambda_dirty = true;
+    return OCEAN_OK;
+}
+
+int ocean_velocity_twin(const ocean_t* c, uint32_t tile, uint32_t* source)
+{
+    if (!c || !source || tile >= c->tiles) return OCEAN_E_INVALID;
+    *source = c->twin_source[tile];
+    return OCEAN_OK;
+}
+
 int ocean_set_params(ocean_t* c, uint32_t tile, const ocean_params* p)
 {
     if (!c || !p) return OCEAN_E_INVALID;
-    if (tile != OCEAN_ALL_TILES && tile >= c->tiles) return OCEAN_E_INVALID;
+    if (tile != OCEAN_ALL_TILES && (tile >= c->tiles || c->twin_source[tile] != OCEAN_NO_SOURCE)) return OCEAN_E_INVALID;    // (a twin has its source's)
     if (!(p->tile_length > 0.0f) || (p->wind_dir_x == 0.0f && p->wind_dir_y == 0.0f)) return OCEAN_E_INVALID;
     for (uint32_t i = 0; i < c->tiles; ++i)
         if (tile == OCEAN_ALL_TILES || tile == i) {
@@ -348,7 +389,7 @@ int ocean_set_params(ocean_t* c, uint32_t tile, const ocean_params* p)
 int ocean_get_params(const ocean_t* c, uint32_t tile, ocean_params* p)
 {
     if (!c || !p || tile >= c->tiles) return OCEAN_E_INVALID;
-    *p = c->params[tile];
+    *p = c->params[effective_tile(c, tile)];
     return OCEAN_OK;
 }
 
@@ -358,7 +399,7 @@ int ocean_set_lambda(ocean_t* c, uint32_t tile, float lambda)
     // the launch arguments when every tile has the same lambda (always so for a single tile), otherwise through
     // one upload of the per-tile array at that frame -- a GUI "Apply" of several setters never drains the device.
     if (!c) return OCEAN_E_INVALID;
-    if (tile != OCEAN_ALL_TILES && tile >= c->tiles) return OCEAN_E_INVALID;
+    if (tile != OCEAN_ALL_TILES && (tile >= c->tiles || c->twin_source[tile] != OCEAN_NO_SOURCE)) return OCEAN_E_INVALID;    // (a twin has its source's)
     for (uint32_t i = 0; i < c->tiles; ++i)
         if (tile == OCEAN_ALL_TILES || tile == i) c->params[i].lambda = lambda;
     c->lambda_dirty = true;
@@ -380,8 +421,7 @@ int ocean_set_tile_size(ocean_t* c, uint32_t tile_size)
     int rc = alloc_device(c);
     if (rc) return rc;
     c->lambda_dirty = true;
-    if (c->use_toff)        // the per-tile time offsets are a property of the context, not of the buffers just re-created
-        HIP_TRY(hipMemcpy(c->toff, c->toff_host.data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
+    if (c->use_toff) OCEAN_TRY(upload_time_offsets(c));        // the per-tile time offsets are a property of the context, not of the buffers just re-created
     return OCEAN_OK;
 }
 
@@ -402,7 +442,7 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
     const size_t n = c->n, n2 = n * n, t = c->tiles;
     std::vector<TileParams> tp(t);
     for (size_t i = 0; i < t; ++i) {
-        const ocean_params& p = c->params[i];
+        const ocean_params& p = c->params[effective_tile(c, (uint32_t)i)];     // (a twin is prepared with its source's: the same k and omega)
         // SetWindDirection: w * (1/sqrt(dot(w,w)))  (.cpp:476-479)
         const float d = p.wind_dir_x * p.wind_dir_x + p.wind_dir_y * p.wind_dir_y;
         const float inv = 1.0f / std::sqrt(d);
@@ -432,6 +472,14 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
                            c->k1d, c->tparams, (int)n);
     }
     HIP_TRY(hipGetLastError());
+    {   // derivative twins: their spectrum becomes i w h0 of their source's, before anything below reads h0
+        for (uint32_t i = 0; i < c->tiles; ++i)                 // (one launch per twin: a batch has few, and the stream orders them)
+            if (c->twin_source[i] != OCEAN_NO_SOURCE)
+                hipLaunchKernelGGL(k_derive_spectrum, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, stream_of(c, 0),
+                                   c->h0, c->omega, c->xi, i, c->twin_source[i], n2);
+        HIP_TRY(hipGetLastError());
+        if (c->use_toff) OCEAN_TRY(upload_time_offsets(c));     // (the table may have changed since they were set)
+    }
     if (c->h0_bits == 16) {
         if (!c->h0h) {
             HIP_TRY(hipMalloc(&c->h0h, t * n2 * sizeof(__half2)));
@@ -574,15 +622,15 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     {   // choppiness: by value when all tiles agree, else the per-tile device array (uploaded when it changed)
         if (c->lambda_dirty) {
             c->lambda_uniform = true;
-            for (uint32_t i = 1; i < c->tiles && c->lambda_uniform; ++i) c->lambda_uniform = c->params[i].lambda == c->params[0].lambda;
+            for (uint32_t i = 1; i < c->tiles && c->lambda_uniform; ++i) c->lambda_uniform = c->params[effective_tile(c, i)].lambda == c->params[effective_tile(c, 0)].lambda;
         }
         const bool uniform = c->lambda_uniform;
-        a.lambda_all = c->params[0].lambda;
+        a.lambda_all = c->params[effective_tile(c, 0)].lambda;
         a.lambda = uniform ? nullptr : c->lambda;
         if (!uniform && c->lambda_dirty) {
             OCEAN_TRY(sync_all(c));                      // frames in flight still read the old array
             std::vector<float> l(c->tiles);
-            for (uint32_t i = 0; i < c->tiles; ++i) l[i] = c->params[i].lambda;
+            for (uint32_t i = 0; i < c->tiles; ++i) l[i] = c->params[effective_tile(c, i)].lambda;
             HIP_TRY(hipMemcpy(c->lambda, l.data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
         }
         c->lambda_dirty = false;
@@ -662,7 +710,7 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     c->frame_valid[set] = true;
     c->tracked[set] = track;
     c->set_lambda[set].resize(c->tiles); c->set_length[set].resize(c->tiles);
-    for (uint32_t i = 0; i < c->tiles; ++i) { c->set_lambda[set][i] = c->params[i].lambda; c->set_length[set][i] = c->prep_length[i]; }
+    for (uint32_t i = 0; i < c->tiles; ++i) { c->set_lambda[set][i] = c->params[effective_tile(c, i)].lambda; c->set_length[set][i] = c->prep_length[i]; }
     c->set_mode[set] = c->mode;
     c->last_t[set] = t; c->last_pipe[set] = pipelined; c->last_handoff[set] = c->handoff;
     if (pipe && !redo) c->frame_ctr++;
@@ -897,7 +945,7 @@ int ocean_set_time_offsets(ocean_t* c, const float* offsets)
     OCEAN_TRY(sync_all(c));
     if (!offsets) { c->use_toff = false; c->toff_host.clear(); return OCEAN_OK; }
     c->toff_host.assign(offsets, offsets + c->tiles);
-    HIP_TRY(hipMemcpy(c->toff, c->toff_host.data(), c->tiles * sizeof(float), hipMemcpyHostToDevice));
+    OCEAN_TRY(upload_time_offsets(c));
     c->use_toff = true;
     return OCEAN_OK;
 }

@@ -106,6 +106,24 @@ __global__ void k_init_spectrum(float2* __restrict__ h0, float* __restrict__ ome
     if (!(steps < 65536.0f)) atomicOr(omega_q_overflow, 1u);
 }
 
+// Derivative twin tiles (include/ocean_consumers.h: ocean_set_velocity_twin).  h~(k, t) = 2 Re(h0 e^{i w t}) has the time derivative
+// 2 Re(i w h0 e^{i w t}): the same expression for the spectrum i w h0 = (-w h0.im, w h0.re), and everything behind the spectrum is linear in
+// it.  Runs behind k_init_spectrum and before anything else reads h0 (fp16 copy, bounds of the half2 intermediates): overwrites every texel of
+// the twin's spectrum from its source's -- same transposed element, one fp32 multiply per component, w the fp32 omega (the float the 16-bit
+// form reconstructs) -- and copies the source's draws into the twin's slot.  The twin's k, omega and omega_q are its source's already: it
+// was initialised with its source's parameters.  One launch per (twin, source).
+__global__ void k_derive_spectrum(float2* __restrict__ h0, const float* __restrict__ omega, float2* __restrict__ xi,
+                                  uint32_t twin, uint32_t source, size_t n2)
+{
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n2) return;
+    const float2 s = h0[source * n2 + i];
+    const float w = omega[source * n2 + i];
+    h0[twin * n2 + i] = make_float2(-(w * s.y), w * s.x);
+    xi[twin * n2 + i] = xi[source * n2 + i];
+}
+
 // fp16 spectrum variant (BASELINE config 4): h0 stored as half2 scaled per tile so
 // that max|component| maps to 2^14 (keeps the small amplitudes normal numbers).
 __global__ void k_h0_absmax(const float2* __restrict__ h0, unsigned* __restrict__ maxbits, size_t n2)

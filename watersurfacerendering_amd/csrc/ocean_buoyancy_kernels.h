@@ -1,8 +1,10 @@
 // ocean_buoyancy_kernels.h -- the kernel behind ocean_buoyancy_bodies (include/ocean_consumers.h), compiled into ocean_consumers.hip only:
 // net force and torque on floating bodies, a segmented reduction over the surface query.  Calls the query's own query_point
 // (ocean_consumer_kernels.h; solve_rest + eval_surface): the water under a hull point is exactly what ocean_query_surface answers there.
+// The flow form (ocean_buoyancy_bodies_flow) is the same kernel with the drag taken against the water's own velocity, read from the derivative
+// twin tiles of the cascade set (ocean_velocity_kernels.h: water_velocity) at the rest point that gave the height.
 #pragma once
-#include "ocean_consumer_kernels.h"
+#include "ocean_velocity_kernels.h"     // (includes ocean_consumer_kernels.h)
 
 namespace ocean {
 
@@ -23,10 +25,14 @@ struct BuoyancyArgs {
     unsigned count;
     float weight;                      // density * gravity, one float product on the host
     float drag;
+    TwinMaps tw;                       // FLOW only: the twins of the cascade set (null otherwise, never read)
 };
 
 constexpr int BUOYANCY_BODIES_PER_BLOCK = 4;
 
+// FLOW = false is ocean_buoyancy_bodies as it always was (query_point in the middle); FLOW = true solves the same rest point itself, because it
+// needs it a second time for the twins' gather: the height and the residual are query_point's expressions, the normal is not formed.
+template <bool FLOW>
 __global__ void __launch_bounds__(256) k_buoyancy_bodies(const BuoyancyArgs b)
 {
 #pragma clang fp contract(off)
@@ -36,6 +42,8 @@ __global__ void __launch_bounds__(256) k_buoyancy_bodies(const BuoyancyArgs b)
     if (body >= b.count) return;
     float amp[OCEAN_MAX_CASCADES];
     query_amplitudes(a, amp);
+    float tamp[OCEAN_MAX_CASCADES];
+    if constexpr (FLOW) twin_amplitudes(a, b.tw, tamp);
 
     const float* w = b.bodies + (size_t)body * 16;
     const float posx = w[0], posy = w[1], posz = w[2];
@@ -61,13 +69,25 @@ __global__ void __launch_bounds__(256) k_buoyancy_bodies(const BuoyancyArgs b)
         const float az = (l.z + qw * t2) + (qx * t1 - qy * t0);
         const float px = posx + ax, py = posy + ay, pz = posz + az;
         // the water under the point is the query's own answer there: H = out_pos.y, the residual = out_nrm.w (the normal is not used)
-        float4 wpos, wnrm;
-        query_point(a, amp, px, pz, wpos, wnrm);
-        const float height = wpos.y, residual = wnrm.w;
+        float height, residual, wvx = 0.0f, wvy = 0.0f, wvz = 0.0f;
+        if constexpr (FLOW) {
+            float rx, rz;
+            solve_rest(a, amp, px, pz, rx, rz);
+            const SurfaceEval ev = eval_surface(a, amp, rx, rz);
+            const float ex = (rx + ev.dx) - px, ez = (rz + ev.dz) - pz;
+            height = 0.0f + ev.dy;
+            residual = sqrtf(ex * ex + ez * ez);
+            water_velocity(a, b.tw, tamp, rx, rz, wvx, wvy, wvz);
+        } else {
+            float4 wpos, wnrm;
+            query_point(a, amp, px, pz, wpos, wnrm);
+            height = wpos.y; residual = wnrm.w;
+        }
         const float s = fminf(fmaxf((height - py) / e + 0.5f, 0.0f), 1.0f);
         const float v = s * ((e * e) * e);
         // the point's own velocity, Archimedes straight up, linear drag in proportion to the submerged volume
-        const float ux = velx + (omy * az - omz * ay), uy = vely + (omz * ax - omx * az), uz = velz + (omx * ay - omy * ax);
+        float ux = velx + (omy * az - omz * ay), uy = vely + (omz * ax - omx * az), uz = velz + (omx * ay - omy * ax);
+        if constexpr (FLOW) { ux = ux - wvx; uy = uy - wvy; uz = uz - wvz; }      // ... relative to the water
         const float dv = b.drag * v;
         const float px_f = -dv * ux, py_f = b.weight * v - dv * uy, pz_f = -dv * uz;
         fx = fx + px_f; fy = fy + py_f; fz = fz + pz_f;

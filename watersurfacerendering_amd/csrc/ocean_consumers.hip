@@ -1,11 +1,11 @@
 // ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
-// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy) and the device memory those calls own.  Their kernels:
-// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_buoyancy_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity) and the device memory those calls own.  Their kernels:
+// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
 #include <cmath>
 
 #include "ocean_ctx.h"
 #include "ocean_foam_kernels.h"     // (includes ocean_consumer_kernels.h)
-#include "ocean_buoyancy_kernels.h"
+#include "ocean_buoyancy_kernels.h" // (includes ocean_velocity_kernels.h)
 
 using namespace ocean;
 
@@ -386,6 +386,62 @@ int ocean_raycast_surface_device(ocean_t* c, const ocean_surface* s, const ocean
 
 }  // extern "C"
 
+// ---- water velocity (include/ocean_consumers.h): the twins of a cascade set, the velocity query ---------------------------------------------
+// The twins of the set's tiles must be the consecutive tiles v, v + 1, ... in cascade order: their maps and keys of frame f.
+static int twin_maps(const ocean_ctx* c, const ocean_surface* s, const LastFrame& f, TwinMaps& tw)
+{
+    uint32_t twin[OCEAN_MAX_CASCADES], found = 0;
+    for (uint32_t k = 0; k < s->cascades; ++k) {
+        twin[k] = OCEAN_NO_SOURCE;
+        for (uint32_t i = 0; i < c->tiles && twin[k] == OCEAN_NO_SOURCE; ++i)
+            if (c->twin_source[i] == s->first_tile + k) twin[k] = i;
+        if (twin[k] != OCEAN_NO_SOURCE) ++found;
+    }
+    if (found == 0) return OCEAN_E_NOT_READY;
+    if (found != s->cascades) return OCEAN_E_INVALID;
+    for (uint32_t k = 1; k < s->cascades; ++k)
+        if (twin[k] != twin[0] + k) return OCEAN_E_INVALID;
+    tw.disp = maps_of(c, f.set).disp + twin[0] * f.n2;
+    tw.minmax = c->minmax[f.set] + 2 * twin[0];
+    return OCEAN_OK;
+}
+
+static int velocity_args(ocean_ctx* c, const ocean_surface* s, LastFrame& f, VelocityArgs& a)
+{
+    OCEAN_TRY(query_args(c, s, f, a.q));
+    a.q.out_nrm = nullptr;
+    return twin_maps(c, s, f, a.tw);
+}
+
+static int launch_velocity(VelocityArgs& a, uint32_t points, const void* d_xz, void* d_out_pos, void* d_out_vel, hipStream_t st)
+{
+    a.q.xz = static_cast<const float2*>(d_xz);
+    a.q.out_pos = static_cast<float4*>(d_out_pos);
+    a.out_vel = static_cast<float4*>(d_out_vel);
+    a.q.points = points;
+    hipLaunchKernelGGL(k_query_velocity, dim3((a.q.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_query_velocity(ocean_t* c, const ocean_surface* s, const float* xz, uint32_t points, float* out_pos, float* out_vel)
+{
+    LastFrame f;
+    VelocityArgs a{};
+    return staged_call(c, velocity_args(c, s, f, a), f, a, launch_velocity, points, xz, 2, out_pos, out_vel, 2);
+}
+
+int ocean_query_velocity_device(ocean_t* c, const ocean_surface* s, const void* d_xz, uint32_t points, void* d_out_pos, void* d_out_vel)
+{
+    LastFrame f;
+    VelocityArgs a{};
+    return device_call(c, velocity_args(c, s, f, a), f, a, launch_velocity, points, d_xz, d_out_pos, d_out_vel, 2);
+}
+
+}  // extern "C"
+
 // ---- persistent foam (include/ocean_consumers.h) -----------------------------------------------------------------------------------------
 // Both buffers or none (as alloc_jacobian): zero-filled on the stream of the update that asked for them.
 static int alloc_foam(ocean_ctx* c, hipStream_t st)
@@ -533,6 +589,7 @@ int ocean_query_foam_device(ocean_t* c, const ocean_surface* s, const void* d_xz
 
 // ---- buoyancy (include/ocean_consumers.h) --------------------------------------------------------------------------------------------------
 // ... of the buoyancy call: the parameters, the surface of the query, then the hull.
+template <bool FLOW>
 static int buoyancy_args(ocean_ctx* c, const ocean_surface* s, const ocean_buoyancy* p, LastFrame& f, BuoyancyArgs& a)
 {
     if (!c || !s || !p || !std::isfinite(p->density) || !std::isfinite(p->gravity) || !std::isfinite(p->drag) ||
@@ -544,9 +601,11 @@ static int buoyancy_args(ocean_ctx* c, const ocean_surface* s, const ocean_buoya
     a.hull_points = c->hull_points;
     a.weight = p->density * p->gravity;
     a.drag = p->drag;
+    if (FLOW) OCEAN_TRY(twin_maps(c, s, f, a.tw));      // (the flow form: the drag is against the twins' velocity)
     return OCEAN_OK;
 }
 
+template <bool FLOW>
 static int launch_buoyancy(BuoyancyArgs& a, uint32_t count, const void* d_bodies, void* d_out_force, void* d_out_torque, hipStream_t st)
 {
     a.bodies = static_cast<const float*>(d_bodies);
@@ -554,7 +613,7 @@ static int launch_buoyancy(BuoyancyArgs& a, uint32_t count, const void* d_bodies
     a.out_torque = static_cast<float4*>(d_out_torque);
     a.count = count;
     const unsigned per_block = BUOYANCY_BODIES_PER_BLOCK;
-    hipLaunchKernelGGL(k_buoyancy_bodies, dim3((unsigned)(((uint64_t)a.count + per_block - 1u) / per_block)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_buoyancy_bodies<FLOW>, dim3((unsigned)(((uint64_t)a.count + per_block - 1u) / per_block)), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return OCEAN_OK;
 }
@@ -595,24 +654,55 @@ int ocean_set_hull(ocean_t* c, const float* points, uint32_t count)
     return OCEAN_OK;
 }
 
-int ocean_buoyancy_bodies(ocean_t* c, const ocean_surface* s, const ocean_buoyancy* b, const ocean_body* bodies, uint32_t count,
-                          float* out_force, float* out_torque)
+}  // extern "C"
+
+// Both forms of the host call: the bodies' ranges are checked against the hull before anything is launched.
+template <bool FLOW>
+static int buoyancy_host(ocean_ctx* c, const ocean_surface* s, const ocean_buoyancy* b, const ocean_body* bodies, uint32_t count,
+                         float* out_force, float* out_torque)
 {
     LastFrame f;
     BuoyancyArgs a{};
-    const int rc = buoyancy_args(c, s, b, f, a);
+    const int rc = buoyancy_args<FLOW>(c, s, b, f, a);
     if (rc == OCEAN_OK && bodies)       // (a NULL array is staged_call's to report)
         for (uint32_t i = 0; i < count; ++i)
             if ((uint64_t)bodies[i].first_point + bodies[i].points > a.hull_points) return OCEAN_E_INVALID;
-    return staged_call(c, rc, f, a, launch_buoyancy, count, reinterpret_cast<const float*>(bodies), 16, out_force, out_torque, 2);
+    return staged_call(c, rc, f, a, launch_buoyancy<FLOW>, count, reinterpret_cast<const float*>(bodies), 16, out_force, out_torque, 2);
+}
+
+template <bool FLOW>
+static int buoyancy_device(ocean_ctx* c, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
+                           void* d_out_force, void* d_out_torque)
+{
+    LastFrame f;
+    BuoyancyArgs a{};
+    return device_call(c, buoyancy_args<FLOW>(c, s, b, f, a), f, a, launch_buoyancy<FLOW>, count, d_bodies, d_out_force, d_out_torque, 2);
+}
+
+extern "C" {
+
+int ocean_buoyancy_bodies(ocean_t* c, const ocean_surface* s, const ocean_buoyancy* b, const ocean_body* bodies, uint32_t count,
+                          float* out_force, float* out_torque)
+{
+    return buoyancy_host<false>(c, s, b, bodies, count, out_force, out_torque);
 }
 
 int ocean_buoyancy_bodies_device(ocean_t* c, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
                                  void* d_out_force, void* d_out_torque)
 {
-    LastFrame f;
-    BuoyancyArgs a{};
-    return device_call(c, buoyancy_args(c, s, b, f, a), f, a, launch_buoyancy, count, d_bodies, d_out_force, d_out_torque, 2);
+    return buoyancy_device<false>(c, s, b, d_bodies, count, d_out_force, d_out_torque);
+}
+
+int ocean_buoyancy_bodies_flow(ocean_t* c, const ocean_surface* s, const ocean_buoyancy* b, const ocean_body* bodies, uint32_t count,
+                               float* out_force, float* out_torque)
+{
+    return buoyancy_host<true>(c, s, b, bodies, count, out_force, out_torque);
+}
+
+int ocean_buoyancy_bodies_flow_device(ocean_t* c, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
+                                      void* d_out_force, void* d_out_torque)
+{
+    return buoyancy_device<true>(c, s, b, d_bodies, count, d_out_force, d_out_torque);
 }
 
 }  // extern "C"

@@ -231,9 +231,15 @@ struct ocean_ctx {
     hipEvent_t frame_done[MAXD] = {};   // recorded on a chain's stream behind the frame whose maps are gathered
     hipEvent_t gather_done[MAXD] = {};  // recorded on the communication stream behind that gather
     bool gather_pending[MAXD] = {};
+    // ---- derivative twin tiles (ocean_set_velocity_twin): [tiles] the source each tile is the twin of, OCEAN_NO_SOURCE for an ordinary tile.
+    // Host state, in effect from the next ocean_prepare; kept across ocean_prepare / ocean_set_tile_size.
+    std::vector<uint32_t> twin_source;
     uint2* pack_half[MAXD][2] = {};    // half-precision copies of a chain's two maps for ocean_gather_maps_f16 (allocated on first use)     // the chain's next frame must wait for gather_done before rewriting the maps
 };
 
+
+// The tile whose ocean_params and time offset tile i runs with: its source where it is a twin, itself otherwise.
+inline uint32_t effective_tile(const ocean_ctx* c, uint32_t i) { return c->twin_source[i] != OCEAN_NO_SOURCE ? c->twin_source[i] : i; }
 
 inline hipStream_t stream_of(const ocean_ctx* c, int set) { return c->user ? c->user : c->own[set]; }
 
