@@ -72,6 +72,9 @@ int ocean_device_mips(ocean_t* ctx, void** d_disp_mips, void** d_nrm_mips, uint3
  * ocean_set_lambda does not change the answer).  fp32 throughout, no contraction (the test suite repeats it step for step).
  * out_nrm.w shows convergence: where the surface folds over itself (Jacobian <= 0) the inverse is not unique, and the
  * residual says so.  K = iterations: 1 .. 32, 0 means 8.
+ * Supported range: finite points whose texel coordinates stay within |u * s_c * N| < 2^31 (N the tile size) at q and at every
+ * r_k.  The out_pos / out_nrm row of a point outside it (NaN, +-inf, beyond 2^31 texels) is unspecified; the texel indices
+ * are masked, so such a point reads inside the maps and leaves every other row as it would be without it.
  * Both calls read the most recently enqueued frame (caller-bound or imported output where it is, as ocean_displace_grid)
  * and are stream-ordered behind it like the other consumers, so the rule of ocean.h holds for them unchanged: a query
  * behind a frame whose in-launch wait gave up gets OCEAN_E_HIP once.

@@ -14,7 +14,8 @@ from oracle.consumer import sample_linear_repeat
 F = np.float32
 
 
-def _eval(disps, nrms, amps, uv_scales, gains, grid, vertex_distance, rx, rz):
+def _eval(disps, nrms, amps, uv_scales, gains, grid, vertex_distance, rx, rz, track=None):
+    """track: a Detail that takes the largest |u * s_c * n| and |v * s_c * n| of this evaluation."""
     half = F(grid // 2)
     u = (rx / F(vertex_distance) + half) / F(grid)
     v = (rz / F(vertex_distance) + half) / F(grid)
@@ -24,6 +25,9 @@ def _eval(disps, nrms, amps, uv_scales, gains, grid, vertex_distance, rx, rz):
     sx, sz, ddx, ddz, jx, jz = z.copy(), z.copy(), z.copy(), z.copy(), z.copy(), z.copy()
     for d, q, amp, sc, g in zip(disps, nrms, amps, uv_scales, gains):
         us, vs = u * F(sc), v * F(sc)
+        if track is not None and len(us):
+            n = F(d.shape[0])
+            track.texel_range = max(track.texel_range, float(np.abs(us * n).max()), float(np.abs(vs * n).max()))
         sd = sample_linear_repeat(d, us, vs)
         sl = sample_linear_repeat(q, us, vs)
         dx = dx + sd[:, 0]; dy = dy + sd[:, 1] * F(amp); dz = dz + sd[:, 2]
@@ -43,9 +47,29 @@ def gains(lambdas, lengths, uv_scales, grid, vertex_distance):
     return [F(lam) * (F(s) * F(L) / den) for lam, L, s in zip(lambdas, lengths, uv_scales)]
 
 
-def query_surface(disps, nrms, amps, lambdas, lengths, uv_scales, grid, vertex_distance, choppy, xz, iterations=8):
+J_CLASSES = ("J >= 0.1", "0 < J < 0.1", "J == 0", "-0.1 < J < 0", "J <= -0.1")
+
+
+def j_census(j):
+    """How many of the unclamped J = 1 + sum_c gain_c * N_c fall into each of J_CLASSES (NaN into none)."""
+    t = F(0.1)
+    return np.array([(j >= t).sum(), ((j > F(0.0)) & (j < t)).sum(), (j == F(0.0)).sum(), ((j < F(0.0)) & (j > -t)).sum(), (j <= -t).sum()],
+                    dtype=np.int64)
+
+
+class Detail:
+    """What query_surface(detail=True) returns beside pos and nrm: the rest point r_K (rx, rz), per Newton step the census of the
+    unclamped J of both axes over J_CLASSES (census [K, 5]), and the largest |u * s_c * n| met in any evaluation (texel_range)."""
+    def __init__(self):
+        self.rx = self.rz = None
+        self.census = []
+        self.texel_range = 0.0
+
+
+def query_surface(disps, nrms, amps, lambdas, lengths, uv_scales, grid, vertex_distance, choppy, xz, iterations=8, detail=False):
     """disps / nrms: per cascade [N, N, 4] maps; amps, lambdas, lengths: per cascade (of the frame that wrote the maps);
-    xz [points, 2].  Returns (pos, nrm), each [points, 4] float32, as ocean_query_surface."""
+    xz [points, 2].  Returns (pos, nrm), each [points, 4] float32, as ocean_query_surface; with detail=True (pos, nrm, Detail)."""
+    det = Detail() if detail else None
     disps = [np.ascontiguousarray(d, dtype=np.float32) for d in disps]
     nrms = [np.ascontiguousarray(q, dtype=np.float32) for q in nrms]
     g = gains(lambdas, lengths, uv_scales, grid, vertex_distance)
@@ -54,12 +78,14 @@ def query_surface(disps, nrms, amps, lambdas, lengths, uv_scales, grid, vertex_d
     rx, rz = qx.copy(), qz.copy()
     k = 8 if iterations == 0 else int(iterations)
     for _ in range(k):
-        dx, _, dz, _, _, _, _, _, jx, jz = _eval(disps, nrms, amps, uv_scales, g, grid, vertex_distance, rx, rz)
+        dx, _, dz, _, _, _, _, _, jx, jz = _eval(disps, nrms, amps, uv_scales, g, grid, vertex_distance, rx, rz, det)
+        if detail:
+            det.census.append(j_census(np.concatenate([F(1.0) + jx, F(1.0) + jz])))
         ex = (rx + dx) - qx
         ez = (rz + dz) - qz
         rx = rx - ex / _clamp(F(1.0) + jx)
         rz = rz - ez / _clamp(F(1.0) + jz)
-    dx, dy, dz, w, sx, sz, ddx, ddz, _, _ = _eval(disps, nrms, amps, uv_scales, g, grid, vertex_distance, rx, rz)
+    dx, dy, dz, w, sx, sz, ddx, ddz, _, _ = _eval(disps, nrms, amps, uv_scales, g, grid, vertex_distance, rx, rz, det)
     px, pz = rx + dx, rz + dz
     ex, ez = px - qx, pz - qz
     pos = np.stack([px, F(0.0) + dy, pz, w], axis=1).astype(np.float32)
@@ -67,4 +93,7 @@ def query_surface(disps, nrms, amps, lambdas, lengths, uv_scales, grid, vertex_d
     nz = -(sz / (F(1.0) + F(choppy) * ddz))
     ln = np.sqrt(nx * nx + F(1.0) + nz * nz)
     nrm = np.stack([nx / ln, F(1.0) / ln, nz / ln, np.sqrt(ex * ex + ez * ez)], axis=1).astype(np.float32)
+    if detail:
+        det.rx, det.rz, det.census = rx, rz, np.array(det.census, dtype=np.int64).reshape(k, len(J_CLASSES))
+        return pos, nrm, det
     return pos, nrm
