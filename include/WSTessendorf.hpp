@@ -225,6 +225,18 @@ public:
     }
     void SetDamping(float damping) { m_Params.damping = damping; Push(); }
 
+    // Beyond the reference: empirical spectra (ocean_set_spectrum) -- the model's sea as a sea state (JONSWAP / TMA / Pierson-Moskowitz,
+    // directional spreading, a wavenumber band) instead of the Phillips spectrum; start from ocean_default_spectrum.  Takes effect at
+    // the next Prepare(), like the reference's setters; wind comes from SetWindDirection / SetWindSpeed.
+    void SetSpectrum(const ocean_spectrum& spectrum) { Check(ocean_set_spectrum(m_Ctx, 0, &spectrum), "ocean_set_spectrum"); }
+    // Hs = 4 sqrt(sum |h0|^2) of the prepared spectrum: in metres for an empirical kind.
+    float GetSignificantWaveHeight()
+    {
+        double m[3];
+        Check(ocean_spectrum_moments(m_Ctx, 0, m), "ocean_spectrum_moments");
+        return 4.0f * (float)std::sqrt(m[0]);
+    }
+
     // Beyond the reference: the device-resident maps (no host copy), for interop.
     ocean_t* Context() const { return m_Ctx; }
 

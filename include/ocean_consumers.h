@@ -1,6 +1,7 @@
 /*
  * include/ocean_consumers.h -- SURVEY.md 8f ranks 3-4: what consumes the two maps on the device (vertex stage, cascades, mip chain).
  * Part of the C ABI of libocean_hip.so (include/ocean.h is the drop-in boundary; this header declares more of the same library's exports).
+ * Also here: what shapes the sea itself beyond the reference's one Phillips spectrum -- empirical spectra, directional spreading, wavenumber bands.
  */
 #ifndef OCEAN_CONSUMERS_H_
 #define OCEAN_CONSUMERS_H_
@@ -312,6 +313,71 @@ int ocean_buoyancy_bodies_flow(ocean_t* ctx, const ocean_surface* s, const ocean
                                float* out_force /* 4 * count */, float* out_torque /* 4 * count */);
 int ocean_buoyancy_bodies_flow_device(ocean_t* ctx, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
                                       void* d_out_force, void* d_out_torque);
+
+/* ---- empirical wave spectra: JONSWAP / TMA, directional spreading, wavenumber bands ---------------------------------------
+ * ocean_params describes the reference's Phillips sea, whose phillips_const is not a physical scale.  ocean_set_spectrum replaces a
+ * tile's spectrum by an empirical one given as a sea state -- wind speed at 10 m (ocean_params.wind_speed, U), fetch F, water depth --
+ * with heights in metres, and/or restricts the tile to a wavenumber band, so that the tiles of a cascade set carry disjoint bands
+ * instead of counting the wavenumbers they share twice.  After Horvath, "Empirical directional wave spectra for computer graphics"
+ * (2015).  Initialisation-time work: the frame kernels and every buffer are unchanged, and a context that never calls this (or sets
+ * ocean_default_spectrum) prepares the same bits as before.
+ * ocean_set_spectrum  host state only, like ocean_set_params: in effect from the next ocean_prepare, kept across ocean_prepare and
+ *          ocean_set_tile_size.  Wind direction and speed come from the tile's ocean_params; the empirical kinds ignore phillips_const
+ *          and damping.  With OCEAN_SPECTRUM_PHILLIPS the sea is the one ocean_params describes and only the band applies.  A twin has
+ *          no spectrum of its own: its explicit index gives OCEAN_E_INVALID, OCEAN_ALL_TILES skips twins, ocean_get_spectrum(twin)
+ *          returns its source's; Prepare derives the twin from its source's new spectrum.
+ * The spectrum   For a bin with k > 1e-5f: k, ux, uz and the unit wind vector (wx, wy) are the floats the Phillips path forms (k =
+ *          sqrtf(kx*kx + kz*kz), u = k-vector * (1.0f / sqrtf(kx*kx + kz*kz))), promoted to double; everything below is in double, g = 9.81
+ *          (the test suite repeats it step for step).
+ *   Frequency    w and dw/dk, continuous (not the quantised omega of the frames, which stays what it is), from ocean_set_dispersion:
+ *                  deep            w = sqrt(g k)                 dw/dk = 0.5 sqrt(g / k)
+ *                  finite depth D  w = sqrt(g k tanh(k D))       dw/dk = g (tanh(k D) + k D (1 - tanh(k D)^2)) / (2 w)
+ *                  capillary L     w = sqrt(g k (1 + k^2 L^2))   dw/dk = g (1 + 3 k^2 L^2) / (2 w)
+ *   Peak, level  resolved on the host at Prepare unless given (alpha / peak_omega != 0):
+ *                  PM              alpha = 0.0081                         wp = 0.855 g / U                   gamma = 1
+ *                  JONSWAP, TMA    alpha = 0.076 (U^2 / (F g))^0.22       wp = 22 (g^2 / (U F))^(1/3)        gamma as given
+ *   S(w)         alpha g^2 w^-5 exp(-1.25 (wp / w)^4) gamma^r,  r = exp(-(w - wp)^2 / (2 sigma^2 wp^2)),  sigma = 0.07 for w <= wp, else 0.09
+ *                TMA multiplies by the Kitaigorodskii factor (Thompson-Vincent), wh = w sqrt(depth / g):
+ *                  0.5 wh^2 for wh <= 1;  1 - 0.5 (2 - wh)^2 for 1 < wh < 2;  1 otherwise
+ *   Spreading    c = clamp(ux wx + uz wy, -1, 1);  D = Q(s) ((1 + c) / 2)^s,
+ *                Q(s) = exp((2 s - 1) ln 2 - ln pi + 2 lgamma(s + 1) - lgamma(2 s + 1))      (the integral of D over direction is 1)
+ *                  OCEAN_SPREAD_COS2S        s = spread_s
+ *                  OCEAN_SPREAD_HASSELMANN   x = w / wp:  s = 6.97 x^4.06 for x <= 1.05,  else 9.77 x^mu,  mu = -2.33 - 1.45 (U wp / g - 1.17)
+ *                then s = s + 16 tanh(wp / w) swell^2
+ *   Amplitude    P = S D (dw/dk) / k (2 pi / L)^2,  L the tile length;  sp = (float)(scale * sqrt(P)), rounded once; then in fp32, no
+ *                contraction, as the Phillips path:  h0 = ((s * g.x) * sp, (s * g.y) * sp),  s = 1.0f / sqrtf(2.0f),  g the bin's draw
+ *   Band         h0 = (0, 0) unless k_min <= k and (k_max == 0 or k < k_max), compared in fp32; for every kind, Phillips included
+ *          omega, the draws (generated or injected) and DC are what they are without this call.
+ * Normalisation  the frames animate h~ = 2 Re(h0 e^{i w t}) and take the real part of the transform, so the expected height variance
+ *          is sum |h0|^2 and E|h0|^2 = P; with dk = 2 pi / L, sum P is a Riemann sum of m0 = integral of S dw.  Heights, and the
+ *          amplitude A of a frame, are in metres.
+ * ocean_get_spectrum  what was set, with alpha / peak_omega as the most recent ocean_prepare resolved them (as set before the first).
+ * ocean_spectrum_moments  synchronises and returns, for whatever the tile's prepared spectrum buffer holds (a twin's: the derivative
+ *          spectrum):  out[0] = sum |h0|^2 (m0 in m^2: the significant wave height is Hs = 4 sqrt(out[0])),  out[1] = sum k |h0|^2,
+ *          out[2] = sum k^2 |h0|^2 (the expected mean-square slope); k the bin's fp32 wavenumber.  Summed on the device in double in a
+ *          fixed order: the same spectrum gives the same bits on every call.
+ * Errors: OCEAN_E_INVALID for a NULL argument, a tile outside the batch, an unknown kind or spreading, a non-finite field; fetch,
+ * gamma, spread_s or scale <= 0; depth <= 0 with TMA; swell outside [0, 1]; a negative alpha, peak_omega, k_min or k_max; k_max != 0
+ * with k_max <= k_min.  ocean_spectrum_moments: OCEAN_E_NOT_READY before Prepare.  (An addition to ABI version 5.)               */
+enum { OCEAN_SPECTRUM_PHILLIPS = 0, OCEAN_SPECTRUM_PM = 1, OCEAN_SPECTRUM_JONSWAP = 2, OCEAN_SPECTRUM_TMA = 3 };
+enum { OCEAN_SPREAD_COS2S = 0, OCEAN_SPREAD_HASSELMANN = 1 };
+typedef struct ocean_spectrum {
+    uint32_t kind, spreading;
+    float fetch;                       /* m; JONSWAP / TMA                                            default 100e3 */
+    float gamma;                       /* peak enhancement; JONSWAP / TMA                             default 3.3   */
+    float depth;                       /* m, > 0; TMA only                                            default 20    */
+    float spread_s;                    /* exponent s of OCEAN_SPREAD_COS2S, > 0                       default 8     */
+    float swell;                       /* 0 .. 1, adds 16 tanh(wp / w) swell^2 to s                   default 0     */
+    float alpha;                       /* 0 = derive from wind and fetch */
+    float peak_omega;                  /* rad/s, 0 = derive */
+    float k_min, k_max;                /* band in rad/m: h0 = 0 unless k_min <= k < k_max; k_max == 0: no upper limit.  EVERY kind */
+    float scale;                       /* multiplies the amplitude sqrt(P) of an empirical kind       default 1     */
+} ocean_spectrum;
+
+void ocean_default_spectrum(ocean_spectrum* s);     /* Phillips, COS2S, the defaults above, band [0, inf): the sea of ocean_params alone */
+int ocean_set_spectrum(ocean_t* ctx, uint32_t tile /* or OCEAN_ALL_TILES */, const ocean_spectrum* s);
+int ocean_get_spectrum(const ocean_t* ctx, uint32_t tile, ocean_spectrum* s);
+int ocean_spectrum_moments(ocean_t* ctx, uint32_t tile, double out[3]);
 
 #ifdef __cplusplus
 }

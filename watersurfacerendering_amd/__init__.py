@@ -48,6 +48,7 @@ class OceanBatch:
         _abi.check(self._L.ocean_create(C.byref(self._h), tile_size, tiles, device), "ocean_create")
         self.tiles = tiles
         self.device = device
+        self._spectra = {}     # tile -> struct ocean_spectrum as set_spectrum last set it
         self._twins = {}       # twin -> source, as ocean_set_velocity_twin accepted them (what set_params(ALL_TILES) skips)
 
     # -- lifetime ---------------------------------------------------------------
@@ -103,6 +104,35 @@ class OceanBatch:
         src = C.c_uint32()
         _abi.check(self._L.ocean_velocity_twin(self._h, int(tile), C.byref(src)), "ocean_velocity_twin")
         return None if src.value == _abi.OCEAN_NO_SOURCE else int(src.value)
+
+    # -- empirical spectra (include/ocean_consumers.h: ocean_set_spectrum) ---------------------------------------------------
+    def set_spectrum(self, tile: int = _abi.OCEAN_ALL_TILES, **fields):
+        """Patch the given fields of struct ocean_spectrum -- kind, spreading, fetch, gamma, depth, spread_s, swell, alpha, peak_omega,
+        k_min, k_max, scale -- of one tile, or of every tile that is not a twin (ocean_set_spectrum); in effect from the next prepare().
+        The fields patched are the ones last SET here (alpha / peak_omega 0 = derive stay 0), not the resolved values spectrum() reports."""
+        tiles = [i for i in range(self.tiles) if i not in self._twins] if tile == _abi.OCEAN_ALL_TILES else (int(tile),)
+        for i in tiles:
+            s = _abi.Spectrum()
+            C.memmove(C.byref(s), C.byref(self._spectra[i]), C.sizeof(s)) if i in self._spectra else self._L.ocean_default_spectrum(C.byref(s))
+            for k, v in fields.items():
+                if k not in dict(_abi.Spectrum._fields_):
+                    raise TypeError(f"unknown spectrum field {k!r}")
+                setattr(s, k, int(v) if k in ("kind", "spreading") else float(v))
+            _abi.check(self._L.ocean_set_spectrum(self._h, i, C.byref(s)), "ocean_set_spectrum")
+            self._spectra[i] = s
+
+    def spectrum(self, tile: int = 0) -> "_abi.Spectrum":
+        """struct ocean_spectrum of `tile` (a twin: its source's), alpha / peak_omega as the last prepare() resolved them (ocean_get_spectrum)."""
+        s = _abi.Spectrum()
+        _abi.check(self._L.ocean_get_spectrum(self._h, int(tile), C.byref(s)), "ocean_get_spectrum")
+        return s
+
+    def spectrum_moments(self, tile: int = 0) -> np.ndarray:
+        """(sum |h0|^2, sum k |h0|^2, sum k^2 |h0|^2) of the tile's prepared spectrum as float64 (ocean_spectrum_moments): the height
+        variance m0 in m^2 -- Hs = 4 sqrt(m0) --, the first moment, the mean-square slope.  Synchronises."""
+        out = (C.c_double * 3)()
+        _abi.check(self._L.ocean_spectrum_moments(self._h, int(tile), out), "ocean_spectrum_moments")
+        return np.array(out[:], dtype=np.float64)
 
     def set_tile_size(self, n: int):
         _abi.check(self._L.ocean_set_tile_size(self._h, n), "ocean_set_tile_size")
@@ -773,6 +803,15 @@ class WSTessendorf:
     def SetPhillipsConst(self, A: float): self._b.set_params(phillips_const=A)
     def SetLambda(self, lam: float): self._b.set_lambda(lam)
     def SetDamping(self, damping: float): self._b.set_params(damping=damping)
+
+    # -- beyond the reference: empirical spectra (include/WSTessendorf.hpp: SetSpectrum / GetSignificantWaveHeight) -------------
+    def SetSpectrum(self, **fields):
+        """Patch fields of the model's struct ocean_spectrum (kind, spreading, fetch, ... k_min, k_max, scale); next Prepare()."""
+        self._b.set_spectrum(0, **fields)
+
+    def GetSignificantWaveHeight(self) -> float:
+        """Hs = 4 sqrt(sum |h0|^2) of the prepared spectrum, in metres for an empirical kind (ocean_spectrum_moments)."""
+        return 4.0 * math.sqrt(float(self._b.spectrum_moments(0)[0]))
 
     # -- beyond the reference: surface query (include/WSTessendorf.hpp: QuerySurface) -----------------------------------
     def QuerySurface(self, xz, positions: np.ndarray | None = None, normals: np.ndarray | None = None, iterations: int = 8):

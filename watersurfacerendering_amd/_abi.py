@@ -27,6 +27,8 @@ OCEAN_COMM_ID_BYTES = 128
 OCEAN_ALL_TILES = 0xFFFFFFFF
 OCEAN_NO_SOURCE = 0xFFFFFFFF       # ocean_set_velocity_twin: an ordinary tile
 OCEAN_MODE_FULL7, OCEAN_MODE_CHOPPY5, OCEAN_MODE_HEIGHT1, OCEAN_MODE_JACOBIAN = 0, 1, 2, 3
+OCEAN_SPECTRUM_PHILLIPS, OCEAN_SPECTRUM_PM, OCEAN_SPECTRUM_JONSWAP, OCEAN_SPECTRUM_TMA = 0, 1, 2, 3     # ocean_spectrum.kind
+OCEAN_SPREAD_COS2S, OCEAN_SPREAD_HASSELMANN = 0, 1                                                      # ocean_spectrum.spreading
 
 #: every symbol the library's three headers declare (tests check the .so exports each one, and that each list equals its header's)
 SYMBOLS_BOUNDARY = [        # include/ocean.h: the drop-in boundary
@@ -47,6 +49,7 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_default_buoyancy", "ocean_set_hull", "ocean_buoyancy_bodies", "ocean_buoyancy_bodies_device",
     "ocean_set_velocity_twin", "ocean_velocity_twin", "ocean_query_velocity", "ocean_query_velocity_device",
     "ocean_buoyancy_bodies_flow", "ocean_buoyancy_bodies_flow_device",
+    "ocean_default_spectrum", "ocean_set_spectrum", "ocean_get_spectrum", "ocean_spectrum_moments",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
     "ocean_read_spectrum", "ocean_read_xi",
@@ -109,6 +112,13 @@ class Body(C.Structure):
 class Buoyancy(C.Structure):
     """struct ocean_buoyancy (include/ocean_consumers.h): water density, gravity and the linear drag per submerged volume."""
     _fields_ = [("density", C.c_float), ("gravity", C.c_float), ("drag", C.c_float)]
+
+
+class Spectrum(C.Structure):
+    """struct ocean_spectrum (include/ocean_consumers.h): a tile's empirical spectrum, directional spreading and wavenumber band."""
+    _fields_ = [("kind", C.c_uint32), ("spreading", C.c_uint32), ("fetch", C.c_float), ("gamma", C.c_float), ("depth", C.c_float),
+                ("spread_s", C.c_float), ("swell", C.c_float), ("alpha", C.c_float), ("peak_omega", C.c_float),
+                ("k_min", C.c_float), ("k_max", C.c_float), ("scale", C.c_float)]
 
 
 last_build = ""      # what the most recent build() did, for the caller to log
@@ -264,6 +274,10 @@ def lib() -> C.CDLL:
         "ocean_query_velocity_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_buoyancy_bodies_flow": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_buoyancy_bodies_flow_device": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_default_spectrum": (None, [C.POINTER(Spectrum)]),
+        "ocean_set_spectrum": (i32, [P, u32, C.POINTER(Spectrum)]),
+        "ocean_get_spectrum": (i32, [P, u32, C.POINTER(Spectrum)]),
+        "ocean_spectrum_moments": (i32, [P, u32, C.POINTER(C.c_double)]),
         "ocean_set_mode": (i32, [P, i32]),
         "ocean_set_dispersion": (i32, [P, i32, f32]),
         "ocean_set_spectrum_precision": (i32, [P, i32]),

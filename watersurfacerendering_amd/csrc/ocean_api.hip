@@ -52,13 +52,14 @@ static void release_import(ocean_ctx* c);
 static void free_device(ocean_ctx* c)
 {
     void* bufs[] = {c->h0, c->omega, c->omega_q, c->base_freq, c->omega_q_overflow, c->k1d, c->tw, c->toff, c->lambda, c->tparams, c->xi,
-                    c->h0h, c->h0_inv_scale, c->h0_maxbits, c->zscale, c->zbounds};
+                    c->h0h, c->h0_inv_scale, c->h0_maxbits, c->zscale, c->zbounds, c->sparams, c->moments};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (int i = 0; i < MAXD; ++i) free_set(c, i);
     c->h0 = nullptr; c->omega = nullptr; c->omega_q = nullptr; c->base_freq = nullptr; c->omega_q_overflow = nullptr;
     c->k1d = nullptr; c->tw = nullptr;
     c->toff = nullptr; c->lambda = nullptr; c->tparams = nullptr; c->xi = nullptr;
     c->h0h = nullptr; c->h0_inv_scale = nullptr; c->h0_maxbits = nullptr; c->zscale = nullptr; c->zbounds = nullptr;
+    c->sparams = nullptr; c->moments = nullptr;
     ocean_consumers_release(c, false);
     c->prepared = false; c->placement_done = false;
     // nothing of the old buffers may be referred to any more: no frame, no chain to read out (no mips or grid of the old maps: above)
@@ -286,6 +287,10 @@ int ocean_create(ocean_t** out, uint32_t tile_size, uint32_t tiles, int device)
     c->cu_count = prop.multiProcessorCount;
     c->params.resize(tiles);
     c->twin_source.assign(tiles, OCEAN_NO_SOURCE);
+    c->spectrum.resize(tiles);
+    for (auto& sp : c->spectrum) ocean_default_spectrum(&sp);
+    c->spectrum_alpha.assign(tiles, 0.0f);
+    c->spectrum_peak.assign(tiles, 0.0f);
     for (auto& p : c->params) ocean_default_params(&p);
     int rc = OCEAN_OK;
     do {
@@ -333,6 +338,58 @@ void ocean_destroy(ocean_t* c)
 int ocean_set_lambda(ocean_t* c, uint32_t tile, float lambda);
 
 }  // extern "C"
+
+// Empirical spectra and bands (ocean_set_spectrum), behind k_init_spectrum: resolves every tile's peak and level in double, uploads the
+// table and runs k_shape_spectrum.  A context whose tiles are all the default sea launches nothing here.  tp: the tiles' TileParams as
+// ocean_prepare has just uploaded them (the fp32 wind speed and tile length the spectrum kernel reads).
+static int shape_spectra(ocean_ctx* c, const std::vector<TileParams>& tp)
+{
+    const size_t n = c->n, n2 = n * n, t = c->tiles;
+    const double g = 9.81;
+    std::vector<SpecParams> sp(t);
+    bool any = false;
+    for (size_t i = 0; i < t; ++i) {
+        SpecParams& d = sp[i];
+        std::memset(&d, 0, sizeof d);
+        if (c->twin_source[i] != OCEAN_NO_SOURCE) continue;         // (k_derive_spectrum writes a twin from its source's shaped spectrum)
+        const ocean_spectrum& s = c->spectrum[i];
+        d.kind = s.kind; d.spreading = s.spreading;
+        d.k_min = s.k_min; d.k_max = s.k_max;
+        d.active = s.kind != OCEAN_SPECTRUM_PHILLIPS || s.k_min > 0.0f || s.k_max != 0.0f;
+        double alpha = s.alpha, wp = s.peak_omega;
+        if (s.kind != OCEAN_SPECTRUM_PHILLIPS) {
+            const double U = tp[i].wind_speed, F = s.fetch;
+            if (s.kind == OCEAN_SPECTRUM_PM) {
+                if (alpha == 0.0) alpha = 0.0081;
+                if (wp == 0.0) wp = 0.855 * g / U;
+                d.gamma = 1.0;
+            } else {
+                if (alpha == 0.0) alpha = 0.076 * std::pow(U * U / (F * g), 0.22);
+                if (wp == 0.0) wp = 22.0 * std::pow(g * g / (U * F), 1.0 / 3.0);
+                d.gamma = s.gamma;
+            }
+            d.alpha = alpha; d.peak_omega = wp;
+            d.tma_depth = s.depth;
+            d.spread_s = s.spread_s;
+            d.hass_mu = -2.33 - 1.45 * (U * wp / g - 1.17);
+            d.swell2 = (double)s.swell * (double)s.swell;
+            const double dk = 2.0 * M_PI / (double)tp[i].length;
+            d.dk2 = dk * dk;
+            d.scale = s.scale;
+            d.dispersion = c->dispersion;
+            d.dispersion_param = c->dispersion_param;
+        }
+        c->spectrum_alpha[i] = (float)alpha; c->spectrum_peak[i] = (float)wp;
+        any = any || d.active;
+    }
+    if (!any) return OCEAN_OK;
+    if (!c->sparams) HIP_TRY(hipMalloc(&c->sparams, t * sizeof(SpecParams)));
+    HIP_TRY(hipMemcpy(c->sparams, sp.data(), t * sizeof(SpecParams), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_shape_spectrum, dim3((unsigned)((n2 + 255) / 256), (unsigned)t), dim3(256), 0, stream_of(c, 0),
+                       c->h0, c->xi, c->k1d, c->tparams, c->sparams, (int)n);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
 
 // The per-tile time offsets as the frames read them: the caller's, a twin with its source's.
 static int upload_time_offsets(ocean_ctx* c)
@@ -406,6 +463,65 @@ int ocean_set_lambda(ocean_t* c, uint32_t tile, float lambda)
     return OCEAN_OK;
 }
 
+// ---- empirical spectra (include/ocean_consumers.h) ---------------------------------------------------------------------------------
+void ocean_default_spectrum(ocean_spectrum* s)
+{
+    if (!s) return;
+    s->kind = OCEAN_SPECTRUM_PHILLIPS; s->spreading = OCEAN_SPREAD_COS2S;
+    s->fetch = 100e3f; s->gamma = 3.3f; s->depth = 20.0f;
+    s->spread_s = 8.0f; s->swell = 0.0f;
+    s->alpha = 0.0f; s->peak_omega = 0.0f;
+    s->k_min = 0.0f; s->k_max = 0.0f;
+    s->scale = 1.0f;
+}
+
+int ocean_set_spectrum(ocean_t* c, uint32_t tile, const ocean_spectrum* s)
+{
+    if (!c || !s) return OCEAN_E_INVALID;
+    if (tile != OCEAN_ALL_TILES && (tile >= c->tiles || c->twin_source[tile] != OCEAN_NO_SOURCE)) return OCEAN_E_INVALID;    // (a twin has its source's)
+    if (s->kind > OCEAN_SPECTRUM_TMA || s->spreading > OCEAN_SPREAD_HASSELMANN) return OCEAN_E_INVALID;
+    for (float v : {s->fetch, s->gamma, s->depth, s->spread_s, s->swell, s->alpha, s->peak_omega, s->k_min, s->k_max, s->scale})
+        if (!std::isfinite(v)) return OCEAN_E_INVALID;
+    if (!(s->fetch > 0.0f) || !(s->gamma > 0.0f) || !(s->spread_s > 0.0f) || !(s->scale > 0.0f)) return OCEAN_E_INVALID;
+    if (s->kind == OCEAN_SPECTRUM_TMA && !(s->depth > 0.0f)) return OCEAN_E_INVALID;
+    if (s->swell < 0.0f || s->swell > 1.0f) return OCEAN_E_INVALID;
+    if (s->alpha < 0.0f || s->peak_omega < 0.0f || s->k_min < 0.0f || s->k_max < 0.0f) return OCEAN_E_INVALID;
+    if (s->k_max != 0.0f && s->k_max <= s->k_min) return OCEAN_E_INVALID;
+    // host state only, like ocean_set_params: the next ocean_prepare picks it up; frames keep using the prepared state until then
+    for (uint32_t i = 0; i < c->tiles; ++i)
+        if ((tile == OCEAN_ALL_TILES && c->twin_source[i] == OCEAN_NO_SOURCE) || tile == i) {
+            c->spectrum[i] = *s;
+            c->spectrum_alpha[i] = s->alpha; c->spectrum_peak[i] = s->peak_omega;
+        }
+    return OCEAN_OK;
+}
+
+int ocean_get_spectrum(const ocean_t* c, uint32_t tile, ocean_spectrum* s)
+{
+    if (!c || !s || tile >= c->tiles) return OCEAN_E_INVALID;
+    const uint32_t e = effective_tile(c, tile);
+    *s = c->spectrum[e];
+    s->alpha = c->spectrum_alpha[e]; s->peak_omega = c->spectrum_peak[e];
+    return OCEAN_OK;
+}
+
+int ocean_spectrum_moments(ocean_t* c, uint32_t tile, double out[3])
+{
+    if (!c || !out || tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!c->prepared) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    const size_t n = c->n;
+    if (!c->moments) HIP_TRY(hipMalloc(&c->moments, (3 * n + 3) * sizeof(double)));
+    hipStream_t st = stream_of(c, 0);
+    hipLaunchKernelGGL(k_moments_columns, dim3((unsigned)n), dim3(256), 0, st, c->h0 + tile * n * n, c->k1d + tile * n, c->moments, (int)n);
+    hipLaunchKernelGGL(k_moments_total, dim3(1), dim3(256), 0, st, c->moments, c->moments + 3 * n, (int)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, c->moments + 3 * n, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return OCEAN_OK;
+}
+
 int ocean_set_tile_size(ocean_t* c, uint32_t tile_size)
 {
     if (!c) return OCEAN_E_INVALID;
@@ -472,6 +588,7 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
                            c->k1d, c->tparams, (int)n);
     }
     HIP_TRY(hipGetLastError());
+    OCEAN_TRY(shape_spectra(c, tp));
     {   // derivative twins: their spectrum becomes i w h0 of their source's, before anything below reads h0
         for (uint32_t i = 0; i < c->tiles; ++i)                 // (one launch per twin: a batch has few, and the stream orders them)
             if (c->twin_source[i] != OCEAN_NO_SOURCE)

@@ -1,8 +1,9 @@
 // ocean_aux_kernels.h -- the kernels around the frame path, compiled into ocean_api.hip only: Prepare() (wave vectors, gaussian draws, base
 // spectrum and quantised dispersion: WSTessendorf.cpp:36-148), the fp16 copy of the spectrum and the bounds of the half2 intermediates, the
-// half-precision pack of the gather.  The consumers' kernels are in ocean_consumer_kernels.h and ocean_foam_kernels.h (ocean_consumers.hip).
+// half-precision pack of the gather, the empirical spectra and the spectrum's moments.  The consumers' kernels are in ocean_consumer_kernels.h and ocean_foam_kernels.h (ocean_consumers.hip).
 // The frame kernels themselves are in ocean_kernels.h.
 #pragma once
+#include "../../include/ocean_consumers.h"      // OCEAN_SPECTRUM_*, OCEAN_SPREAD_*
 #include "ocean_kernels.h"
 
 namespace ocean {
@@ -104,6 +105,152 @@ __global__ void k_init_spectrum(float2* __restrict__ h0, float* __restrict__ ome
     // 4 per texel) and rebuild the same float, float(steps) * base_freq, unless some multiple needs more bits
     omega_q[tile * n2 + i] = (uint16_t)(steps < 65536.0f ? (unsigned)steps : 0u);
     if (!(steps < 65536.0f)) atomicOr(omega_q_overflow, 1u);
+}
+
+// Empirical spectra and wavenumber bands (include/ocean_consumers.h: ocean_set_spectrum).  One entry per tile, resolved on the host at
+// ocean_prepare: the peak, the level and every constant of the tile in double.  active == 0: the default sea (or a twin, whose spectrum
+// k_derive_spectrum writes): k_shape_spectrum leaves the tile alone.
+struct SpecParams {
+    uint32_t active;         // 0: nothing to do for this tile
+    uint32_t kind;           // OCEAN_SPECTRUM_*
+    uint32_t spreading;      // OCEAN_SPREAD_*
+    int dispersion;          // the context's dispersion kind: the continuous omega and d omega / dk
+    float k_min, k_max;      // the band, compared with the fp32 k; k_max == 0: no upper limit
+    double dispersion_param;
+    double alpha, peak_omega, gamma;
+    double tma_depth;
+    double spread_s;         // COS2S exponent
+    double hass_mu;          // Hasselmann's exponent beyond 1.05 omega_p: -2.33 - 1.45 (U omega_p / g - 1.17)
+    double swell2;           // swell^2
+    double dk2;              // (2 pi / L)^2
+    double scale;
+};
+
+// sqrt(P) of one bin, in double throughout: the text of include/ocean_consumers.h ("The spectrum") line for line.
+__device__ inline double empirical_amplitude(const SpecParams& sp, double k, double c)
+{
+#pragma clang fp contract(off)
+    const double g = 9.81;
+    double w, dwdk;
+    if (sp.dispersion == 1) {
+        const double kd = k * sp.dispersion_param, th = tanh(kd);
+        w = sqrt(g * k * th);
+        dwdk = g * (th + kd * (1.0 - th * th)) / (2.0 * w);
+    } else if (sp.dispersion == 2) {
+        const double kl2 = k * k * sp.dispersion_param * sp.dispersion_param;
+        w = sqrt(g * k * (1.0 + kl2));
+        dwdk = g * (1.0 + 3.0 * kl2) / (2.0 * w);
+    } else {
+        w = sqrt(g * k);
+        dwdk = 0.5 * sqrt(g / k);
+    }
+    const double wp = sp.peak_omega;
+    const double pw = wp / w, pw2 = pw * pw;
+    const double sigma = w <= wp ? 0.07 : 0.09;
+    const double dw = w - wp;
+    const double r = exp(-(dw * dw) / (2.0 * sigma * sigma * wp * wp));
+    const double w2 = w * w;
+    double S = sp.alpha * g * g / (w2 * w2 * w) * exp(-1.25 * (pw2 * pw2)) * pow(sp.gamma, r);
+    if (sp.kind == OCEAN_SPECTRUM_TMA) {
+        const double wh = w * sqrt(sp.tma_depth / g);
+        if (wh <= 1.0) S *= 0.5 * wh * wh;
+        else if (wh < 2.0) S *= 1.0 - 0.5 * (2.0 - wh) * (2.0 - wh);
+    }
+    double s;
+    if (sp.spreading == OCEAN_SPREAD_HASSELMANN) {
+        const double x = w / wp;
+        s = x <= 1.05 ? 6.97 * pow(x, 4.06) : 9.77 * pow(x, sp.hass_mu);
+    } else {
+        s = sp.spread_s;
+    }
+    s += 16.0 * tanh(pw) * sp.swell2;
+    const double lnQ = (2.0 * s - 1.0) * 0.69314718055994530942 - 1.1447298858494001741 + 2.0 * lgamma(s + 1.0) - lgamma(2.0 * s + 1.0);
+    const double D = exp(lnQ) * pow(0.5 * (1.0 + c), s);
+    const double P = S * D * dwdk / k * sp.dk2;
+    return sp.scale * sqrt(P);
+}
+
+// Runs behind k_init_spectrum and before k_derive_spectrum.  A tile with an empirical kind gets h0 = ((s g.x) sp, (s g.y) sp) from the draws
+// in xi (generated or injected: k_init_spectrum has left them there), sp the double amplitude above rounded once; a texel outside the
+// tile's band becomes (0, 0) whatever the kind.  k, ux, uz are formed exactly as k_init_spectrum forms them; omega, omega_q, the draws and
+// DC are not touched.  Same transposed layout: element i is wave index (m, q) = (i % n, i / n), its draw sits at m * n + q.
+__global__ void k_shape_spectrum(float2* __restrict__ h0, const float2* __restrict__ xi, const float* __restrict__ k1d,
+                                 const TileParams* __restrict__ tp, const SpecParams* __restrict__ spec, int n)
+{
+#pragma clang fp contract(off)
+    const int tile = blockIdx.y;
+    if (!spec[tile].active) return;
+    const size_t n2 = (size_t)n * n;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n2) return;
+    const SpecParams sp = spec[tile];
+    const int q = (int)(i / n), m = (int)(i % n);
+    const float kx = k1d[(size_t)tile * n + q], kz = k1d[(size_t)tile * n + m];
+    const float d = kx * kx + kz * kz;
+    const float k = sqrtf(d);
+    if (!(k > 0.00001f)) return;                        // DC stays what k_init_spectrum wrote: (0, 0)
+    if (!(sp.k_min <= k && (sp.k_max == 0.0f || k < sp.k_max))) {
+        h0[tile * n2 + i] = make_float2(0.f, 0.f);
+        return;
+    }
+    if (sp.kind == OCEAN_SPECTRUM_PHILLIPS) return;     // inside the band a Phillips tile keeps its bits
+    const float inv = 1.0f / sqrtf(d);
+    const float ux = kx * inv, uz = kz * inv;
+    const double dot = (double)ux * (double)tp[tile].wind_x + (double)uz * (double)tp[tile].wind_y;
+    const double c = fmin(fmax(dot, -1.0), 1.0);
+    const float a = (float)empirical_amplitude(sp, (double)k, c);
+    const float2 g = xi[tile * n2 + (size_t)m * n + q];
+    const float s = 1.0f / sqrtf(2.0f);
+    h0[tile * n2 + i] = make_float2((s * g.x) * a, (s * g.y) * a);
+}
+
+// ocean_spectrum_moments: sum |h0|^2, sum k |h0|^2, sum k^2 |h0|^2 of one tile, in double, in a fixed order, without atomics: the same
+// spectrum gives the same bits on every run.  k is the fp32 wavenumber of the bin (as k_init_spectrum forms it) promoted to double.
+// Stage 1, one workgroup of 256 per spectrum column (contiguous in the transposed layout): lane l adds elements l, l + 256, ... in that
+// order, then a tree over the 256 lane sums (off = 128 ... 1: slot[l] += slot[l + off]).  Stage 2, one workgroup: the same over the n
+// column sums.
+__device__ inline void moments_tree(double (*sh)[256], double v[3], double* __restrict__ out)
+{
+    for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = v[j];
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = sh[j][threadIdx.x] + sh[j][threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        for (int j = 0; j < 3; ++j) out[j] = sh[j][0];
+}
+
+__global__ void __launch_bounds__(256) k_moments_columns(const float2* __restrict__ h0, const float* __restrict__ k1d,
+                                                         double* __restrict__ colsum, int n)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[3][256];
+    const int col = blockIdx.x;                         // (h0 and k1d point at the tile)
+    const float2* __restrict__ c = h0 + (size_t)col * n;
+    const float kx = k1d[col];
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int e = threadIdx.x; e < n; e += 256) {
+        const float2 a = c[e];
+        const float kz = k1d[e];
+        const double k = (double)sqrtf(kx * kx + kz * kz);
+        const double p = (double)a.x * (double)a.x + (double)a.y * (double)a.y;
+        v[0] = v[0] + p;
+        v[1] = v[1] + k * p;
+        v[2] = v[2] + (k * k) * p;
+    }
+    moments_tree(sh, v, colsum + 3 * (size_t)col);
+}
+
+__global__ void __launch_bounds__(256) k_moments_total(const double* __restrict__ colsum, double* __restrict__ out, int n)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[3][256];
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int col = threadIdx.x; col < n; col += 256)
+        for (int j = 0; j < 3; ++j) v[j] = v[j] + colsum[3 * (size_t)col + j];
+    moments_tree(sh, v, out);
 }
 
 // Derivative twin tiles (include/ocean_consumers.h: ocean_set_velocity_twin).  h~(k, t) = 2 Re(h0 e^{i w t}) has the time derivative

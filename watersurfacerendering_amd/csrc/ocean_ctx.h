@@ -13,6 +13,8 @@
 #include "../../include/ocean_dev.h"
 #include "ocean_kernels.h"
 
+namespace ocean { struct SpecParams; }     // ocean_aux_kernels.h
+
 constexpr int MAXD = 8;     // maximum pipeline depth (independent frame chains)
 constexpr int OCEAN_MAX_LAUNCHES = 3;   // launches per frame: at most three (ocean_launch.h)
 constexpr uint32_t OCEAN_HULL_GUARD = 64;   // NaN points allocated behind the hull of ocean_set_hull (ocean_ctx::hull)
@@ -234,6 +236,12 @@ struct ocean_ctx {
     // ---- derivative twin tiles (ocean_set_velocity_twin): [tiles] the source each tile is the twin of, OCEAN_NO_SOURCE for an ordinary tile.
     // Host state, in effect from the next ocean_prepare; kept across ocean_prepare / ocean_set_tile_size.
     std::vector<uint32_t> twin_source;
+    // ---- empirical spectra (ocean_set_spectrum): [tiles] as the caller set them, and alpha / peak_omega as the most recent ocean_prepare
+    // resolved them (what ocean_get_spectrum reports).  Host state, in effect from the next ocean_prepare; kept across it and ocean_set_tile_size.
+    std::vector<ocean_spectrum> spectrum;
+    std::vector<float> spectrum_alpha, spectrum_peak;
+    ocean::SpecParams* sparams = nullptr;   // [tiles] device table of the resolved spectra; allocated by the first ocean_prepare that has a non-default tile
+    double* moments = nullptr;              // ocean_spectrum_moments: [n][3] column sums, then the three totals; allocated on first use
     uint2* pack_half[MAXD][2] = {};    // half-precision copies of a chain's two maps for ocean_gather_maps_f16 (allocated on first use)     // the chain's next frame must wait for gather_done before rewriting the maps
 };
 
