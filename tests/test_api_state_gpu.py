@@ -567,6 +567,30 @@ def test_compute_waves_read_is_compute_waves_plus_read_maps(n, tiles, depth):
     b.close()
 
 
+@pytest.mark.parametrize("n,depth", [(64, 1), (256, 1), (256, 2), (1024, 1)])
+def test_frames_after_compute_waves_read_leave_its_destinations_alone(n, depth):
+    """The destinations of ocean_compute_waves_read belong to that one call: the frames enqueued after it -- synchronous and asynchronous --
+    store nothing there and start no copy into them.  64^2: merged x pass, no point behind k_xpass_b; 256^2: two x launches that store into
+    the page-locked arrays themselves (depth 2: pipelined); 1024^2: 16 MiB per map, above OceanTuning::host_store_max_bytes -- the copy
+    engines move it, the normal map's copy started behind k_xpass_b."""
+    import watersurfacerendering_amd as W
+    b = W.OceanBatch(n, 1, 0)
+    b.set_pipeline_depth(depth)
+    b.prepare(SEED + 22)
+    d = pinned_array((1, n, n, 4), np.float32, tag="d"); q = pinned_array((1, n, n, 4), np.float32, tag="q")
+    b.compute_waves_read(1.25, d, q)
+    d0, q0 = d.copy(), q.copy()
+    b.compute_waves(7.5)
+    for j in range(depth):
+        b.compute_waves_async(3.0 + j)
+    b.synchronize()
+    assert np.array_equal(d.view(np.uint32), d0.view(np.uint32)) and np.array_equal(q.view(np.uint32), q0.view(np.uint32))
+    dd, qq = b.read_maps()                                # the later frames really ran: the context's maps have moved on
+    assert not np.array_equal(dd, d0) and not np.array_equal(qq, q0)
+    assert b.fault_recoveries == 0
+    b.close()
+
+
 def test_placement_search_changes_no_bit_and_reports():
     """ocean_prepare's placement search (round 6; include/ocean_dev.h): from 2048^2 up Prepare times a few candidate allocations of the spectrum +
     intermediates on serial frames and keeps the fastest -- the same 2048^2 z pass runs 19.8 ... 28.6 us depending on where those buffers landed

@@ -169,6 +169,19 @@ static int alloc_device(ocean_ctx* c)
     return OCEAN_OK;
 }
 
+// One frame as its callers ask for it (enqueue_frame, below).
+struct FrameRequest {
+    float t = 0.0f;
+    bool pipelined = false;             // the call may use the pipeline chains (depth > 1)
+    bool tracked = false;               // the frame counts its finished workgroups and writes its completion records last (ocean_ctx::tracked)
+    int redo_set = -1;                  // >= 0: recover_fault runs this chain's most recent frame again
+    hipEvent_t* marks = nullptr;        // 2 x OCEAN_MAX_LAUNCHES events (start, stop per launch) or null
+    float4* host_disp = nullptr;        // device addresses of the caller's page-locked arrays when the x passes are to store the maps there
+    float4* host_nrm = nullptr;         //   themselves, beside the device copy (FrameArgs::disp_host / nrm_host); null otherwise
+    hipEvent_t after_b = nullptr;       // recorded behind k_xpass_b, where the frame has a displacement pass of its own behind it (null: nothing)
+    bool after_b_recorded = false;      // out: it was (frames whose x axis is one launch -- small tiles -- have no such point)
+};
+
 // An in-launch wait of a merged / one-launch frame that gave up (ocean_kernels.h: wait_counter) has produced a wrong frame: never silently -- and
 // never fatally either (on a shared or time-sliced device a preempted producer is a slow producer, not a broken one).  The host
 // drains the context, clears the word, switches the hand-off forms OFF for this context (launch_frame: c->merged_x) and runs the most recent frame
@@ -176,7 +189,7 @@ static int alloc_device(ocean_ctx* c)
 // read-out returns the frame it asked for.  What cannot be redone is reported once: a stream-ordered consumer (gather, vertex stage, mips)
 // enqueued behind such a frame has consumed it (OCEAN_E_HIP / hipErrorLaunchTimeOut from this call; the context is usable, the consumer call is
 // the caller's to repeat).
-static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* marks, bool track, int redo_set);
+static int enqueue_frame(ocean_ctx* c, FrameRequest& rq);
 static int placement_search(ocean_ctx* c);
 static bool fault_raised(const ocean_ctx* c) { return c->fault && __atomic_load_n(c->fault, __ATOMIC_ACQUIRE) != 0u; }
 static void reset_pipeline_state(ocean_ctx* c)
@@ -208,7 +221,11 @@ static int recover_fault(ocean_ctx* c)
     int rc = OCEAN_OK;
     const int last = c->last_set;
     for (int set = 0; set < MAXD && rc == OCEAN_OK; ++set)
-        if (c->frame_valid[set] && c->last_handoff[set]) rc = enqueue_frame(c, c->last_t[set], c->last_pipe[set], nullptr, c->tracked[set], set);
+        if (c->frame_valid[set] && c->last_handoff[set]) {
+            FrameRequest again;
+            again.t = c->last_t[set]; again.pipelined = c->last_pipe[set]; again.tracked = c->tracked[set]; again.redo_set = set;
+            rc = enqueue_frame(c, again);
+        }
     c->last_set = last;                             // the caller's "most recent frame" is still the one it enqueued last
     if (rc == OCEAN_OK) rc = drain_streams(c);
     c->recovering = false;
@@ -694,21 +711,24 @@ static const char* kernel_name_of(int idx)
     return nullptr;
 }
 
-// Enqueues one frame.  pipelined = the call may use the pipeline chains (depth > 1).  redo_set >= 0: recover_fault runs chain redo_set's most
-// recent frame again (same chain and regime; no burst / rotation bookkeeping, no hand-off form: c->merged_x is off by then).
-static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* marks, bool track = false, int redo_set = -1)
+// Enqueues one frame.  A redone frame (rq.redo_set >= 0) keeps its chain and regime, with no burst / rotation bookkeeping and no hand-off form:
+// c->merged_x is off by then.  Everything the launcher is told and tells travels in a FrameLaunch of this call's own; the context changes only
+// where the comments below say "committed".
+static int enqueue_frame(ocean_ctx* c, FrameRequest& rq)
 {
+    rq.after_b_recorded = false;
     if (!c) return OCEAN_E_INVALID;
     if (!c->prepared) return OCEAN_E_NOT_READY;
     (void)hipGetLastError();        // an earlier, unrelated error of this thread must not be taken for this frame's (launch_frame ends in hipGetLastError)
-    const bool redo = redo_set >= 0;
+    const float t = rq.t;
+    const bool pipelined = rq.pipelined, track = rq.tracked, redo = rq.redo_set >= 0;
     // depth D: frames f, f+1, ... run as D independent chains (own stream, own
     // intermediates, own map set) with no cross-stream dependency at all -- the first
     // pass of one frame fills the memory-idle phases of the others' map passes.
     // Caller-bound output buffers or a caller stream force depth 1.
     const bool pipe = pipelined && c->depth > 1 && !c->user && !c->ext_disp && !c->ext_nrm;
     if (!pipe && c->depth > 1 && pipelined && !redo) OCEAN_TRY(sync_all(c));    // leaving pipelined mode: drain the other chains first
-    const int set = redo ? redo_set : (pipe ? (int)(c->frame_ctr % (uint64_t)c->depth) : 0);
+    const int set = redo ? rq.redo_set : (pipe ? (int)(c->frame_ctr % (uint64_t)c->depth) : 0);
     OCEAN_TRY(alloc_set(c, set));
     hipStream_t st = stream_of(c, set);
     if (c->gather_pending[set]) {        // this chain's maps are still being sent: the frame may not rewrite them yet
@@ -722,7 +742,7 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     a.h0h = (c->h0_bits == 16) ? c->h0h : nullptr; a.h0_inv_scale = c->h0_inv_scale;
     a.zscale = c->zscale;
     a.z = c->z[set]; a.zh = c->zh[set]; a.hraw = c->hraw[set]; a.minmax = c->minmax[set]; a.hdone = c->hdone[set];
-    a.zdone = c->zdone[set]; a.zdone_target = 0; a.poll_sleep = 0; a.fault = c->fault; c->cur_set = set;
+    a.zdone = c->zdone[set]; a.zdone_target = 0; a.poll_sleep = 0; a.fault = c->fault;
     a.z3 = c->z3[set]; a.jraw = c->jraw[set]; a.jac0 = c->jac0[set];
     a.done_rec = c->done_rec[set]; a.done_ctr = track ? c->done_ctr[set] : nullptr;
     // The chain's sequence number is committed at once and never reused while the record buffer lives (a frame whose enqueue fails half way
@@ -755,23 +775,25 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     a.t = t;
     a.mode = c->mode;
     a.start_ramp = 0;       // (set per launch by the launcher where a staggered start pays: ocean_launch.h)
-    a.disp_host = c->host_out[0]; a.nrm_host = c->host_out[1];      // (ocean_compute_waves_read, small maps; null otherwise)
+    a.disp_host = rq.host_disp; a.nrm_host = rq.host_nrm;           // (ocean_compute_waves_read, small maps; null otherwise)
     a.zmask = 15; a.xb_roles = 3;                   // (every transform in the one z pass; the x-axis roles per launch: ocean_launch.h)
     a.xcd_rot = 0;
 #ifdef OCEAN_DEVELOPER
     if (const char* xr = getenv("OCEAN_XCD_ROT")) a.xcd_rot = atoi(xr) % 7;      // (read per frame: tools/slow_window.py flips it between windows)
 #endif
     a.rec_mode = track ? 2 : 1;                     // what the frame's LAST launch does with the completion records
-    // maps beyond the memory-side cache, or several frames in flight: stream the maps past it
+    FrameLaunch fl;
+    fl.set = set; fl.stream = st; fl.marks = rq.marks; fl.after_b = rq.after_b;
+    FramePolicy& policy = fl.policy;
     const double texels = (double)c->tiles * (double)c->n * (double)c->n;
     // several frames in flight, or maps that would push everything else out of the 256 MiB memory-side cache anyway
     // (32 B/texel: 4096^2, 8 x 1024^2 ...): stream the maps past it.  A serial 2048^2 frame (134 MB of maps) is
     // faster with plain stores (76 vs 80 us), a serial 8 x 1024^2 batch (268 MB) with streamed ones (124 vs 150 us).
-    int stream_maps = (pipe || texels * 32.0 > c->tune.maps_stream_frac * c->tune.cache_bytes) ? 3 : 0;
-    if (c->inter_bits == 16) stream_maps |= 8;          // bit 3: half2 intermediates (kernel variant, not a store policy)
+    policy.nt_normal = policy.nt_disp = pipe || texels * 32.0 > c->tune.maps_stream_frac * c->tune.cache_bytes;
+    policy.half_inter = c->inter_bits == 16;
     if (pipe) {
         // what every frame re-reads -- spectrum + the intermediates of every chain in flight -- against the memory-side
-        // cache: beyond it the intermediates are streamed too (bit 2, see store_z; the z pass then takes two columns per
+        // cache: beyond it the intermediates are streamed too (see store_z; the z pass then takes two columns per
         // workgroup so that the streamed stores cover whole lines).  Never for a serial frame: its x pass reads them right
         // behind the z pass (4096^2 serial 321-324 either way, 8 x 1024^2 serial 126 vs 136 us, depth 2 124 vs 114 us;
         // 2048^2 depth 3 -- 243 MB -- 57-58 plain vs 59-60 streamed, depth 4 -- 310 MB -- 61 vs 58.5;
@@ -782,12 +804,15 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
         const bool jac = c->mode == OCEAN_MODE_JACOBIAN;
         const double inter = c->inter_bits == 16 ? (jac ? 14.0 : 8.0) : (jac ? 22.0 : 16.0);
         const double resident = texels * (10.0 + inter * c->depth);
-        if (resident > c->tune.inter_stream_frac * c->tune.cache_bytes) stream_maps |= 4;
+        policy.nt_inter = resident > c->tune.inter_stream_frac * c->tune.cache_bytes;
     }
-    if (!pipe) stream_maps |= 16;                                               // this frame has the device to itself (which staggered start: ocean_launch.h)
+    policy.alone = !pipe;
 #ifdef OCEAN_DEVELOPER      // A/B builds only: the shipped library reads no environment
-    static const char* const stream_env = getenv("OCEAN_STREAM_MAPS");          // bit mask of the store policies
-    if (stream_env) stream_maps = (atoi(stream_env) & 7) | (stream_maps & 24);
+    static const char* const stream_env = getenv("OCEAN_STREAM_MAPS");          // bit mask of the three store policies: 1 normal map, 2 displacement map, 4 intermediates
+    if (stream_env) {
+        const int mask = atoi(stream_env);
+        policy.nt_normal = (mask & 1) != 0; policy.nt_disp = (mask & 2) != 0; policy.nt_inter = (mask & 4) != 0;
+    }
 #endif
     // The first frames after a drain start STAGGERED: chains that begin together run the same kind of kernel side by side -- three z passes,
     // then three normal-map passes ... -- and stay in that lockstep for dozens of frames (in the steady state one chain runs half a period
@@ -797,20 +822,19 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     // chaining EVERY frame's z pass instead costs 8 us per frame: profiles/r04_zpass_experiments.txt item 5).
     // (the burst state -- burst_pos, z_last_set -- is committed below, once the launches have succeeded; the stream wait enqueued here is
     //  harmless if they do not: a wait for an event that has been recorded already)
-    c->after_z = nullptr;
     const bool stagger = pipe && !redo && c->burst_pos < c->depth;
     if (stagger) {
         if (!c->z_done[set]) HIP_TRY(hipEventCreateWithFlags(&c->z_done[set], hipEventDisableTiming));
         if (c->z_last_set >= 0 && c->z_last_set != set && c->z_done[c->z_last_set]) HIP_TRY(hipStreamWaitEvent(st, c->z_done[c->z_last_set], 0));
-        c->after_z = c->z_done[set];
+        fl.after_z = c->z_done[set];
     }
     hipError_t e = hipErrorInvalidValue;
-    if (c->n <= 256) e = ocean_launch_frame_small(c, a, stream_maps, st, marks);
-    else if (c->n <= 1024) e = ocean_launch_frame_mid(c, a, stream_maps, st, marks);
-    else if (c->n == 2048) e = ocean_launch_frame_2048(c, a, stream_maps, st, marks);
-    else if (c->n == 4096) e = ocean_launch_frame_4096(c, a, stream_maps, st, marks);
-    else { c->after_z = nullptr; return OCEAN_E_UNSUPPORTED; }
-    c->after_z = nullptr;
+    if (c->n <= 256) e = ocean_launch_frame_small(c, a, fl);
+    else if (c->n <= 1024) e = ocean_launch_frame_mid(c, a, fl);
+    else if (c->n == 2048) e = ocean_launch_frame_2048(c, a, fl);
+    else if (c->n == 4096) e = ocean_launch_frame_4096(c, a, fl);
+    else return OCEAN_E_UNSUPPORTED;
+    rq.after_b_recorded = fl.after_b_recorded;
     if (e != hipSuccess) {
         // some of the frame's launches may have run: the chain's records, height keys and maps no longer describe ONE frame -- the chain has
         // no frame until the next successful enqueue (wait / read-out: OCEAN_E_NOT_READY), the other chains are untouched
@@ -829,7 +853,9 @@ static int enqueue_frame(ocean_ctx* c, float t, bool pipelined, hipEvent_t* mark
     c->set_lambda[set].resize(c->tiles); c->set_length[set].resize(c->tiles);
     for (uint32_t i = 0; i < c->tiles; ++i) { c->set_lambda[set][i] = c->params[effective_tile(c, i)].lambda; c->set_length[set][i] = c->prep_length[i]; }
     c->set_mode[set] = c->mode;
-    c->last_t[set] = t; c->last_pipe[set] = pipelined; c->last_handoff[set] = c->handoff;
+    c->last_t[set] = t; c->last_pipe[set] = pipelined; c->last_handoff[set] = fl.handoff;
+    c->launch_count = fl.launch_count;
+    for (int l = 0; l < fl.launch_count; ++l) c->launch_kernel[l] = fl.launch_kernel[l];
     if (pipe && !redo) c->frame_ctr++;
     c->have_frame = true;
     c->last_set = set;
@@ -893,7 +919,10 @@ static int placement_search(ocean_ctx* c)
     };
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = OCEAN_OK;
-    auto frames = [&](int count) { for (int j = 0; j < count && rc == OCEAN_OK; ++j) rc = enqueue_frame(c, 0.05f * (float)j, false, nullptr, false); };
+    auto frames = [&](int count) {
+        FrameRequest serial;            // (defaults: not pipelined, not tracked)
+        for (int j = 0; j < count && rc == OCEAN_OK; ++j) { serial.t = 0.05f * (float)j; rc = enqueue_frame(c, serial); }
+    };
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = OCEAN_E_HIP;
     // warm-up on the first candidate: 30 ms of frames (host clock), so that every candidate is timed at the sustained shader clock
     const auto w0 = std::chrono::steady_clock::now();
@@ -960,7 +989,9 @@ int ocean_compute_waves_async(ocean_t* c, float t)
 {
     if (!c) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    return enqueue_frame(c, t, true, nullptr, c->track_async);
+    FrameRequest rq;
+    rq.t = t; rq.pipelined = true; rq.tracked = c->track_async;
+    return enqueue_frame(c, rq);
 }
 
 int ocean_set_frame_tracking(ocean_t* c, int on)
@@ -1050,7 +1081,9 @@ int ocean_compute_waves(ocean_t* c, float t, float* out_amp)
 {
     if (!c) return OCEAN_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = enqueue_frame(c, t, true, nullptr, true);
+    FrameRequest rq;
+    rq.t = t; rq.pipelined = true; rq.tracked = true;
+    const int rc = enqueue_frame(c, rq);
     if (rc) return rc;
     return ocean_wait_frame(c, out_amp);        // waits for this frame only
 }
@@ -1114,11 +1147,11 @@ int ocean_compute_waves_read(ocean_t* c, float t, float* out_amp, float* disp, f
         dev_dst[1] = pinned_device_address(nrm, bytes);
     }
     const bool direct = dev_dst[0] && dev_dst[1];
-    c->host_out[0] = direct ? static_cast<float4*>(dev_dst[0]) : nullptr;
-    c->host_out[1] = direct ? static_cast<float4*>(dev_dst[1]) : nullptr;
-    c->after_b = direct ? nullptr : c->nrm_final; c->after_b_recorded = false;
-    int rc = enqueue_frame(c, t, true, nullptr, true);
-    c->after_b = nullptr; c->host_out[0] = c->host_out[1] = nullptr;
+    FrameRequest rq;
+    rq.t = t; rq.pipelined = true; rq.tracked = true;
+    if (direct) { rq.host_disp = static_cast<float4*>(dev_dst[0]); rq.host_nrm = static_cast<float4*>(dev_dst[1]); }
+    else rq.after_b = c->nrm_final;
+    int rc = enqueue_frame(c, rq);
     if (rc) return rc;
     const int set = c->last_set;
     hipStream_t st = stream_of(c, set);
@@ -1126,7 +1159,7 @@ int ocean_compute_waves_read(ocean_t* c, float t, float* out_amp, float* disp, f
     const float4* q = maps_of(c, set).nrm;
     hipStream_t nst = st;
     if (!direct) {
-        if (c->after_b_recorded) {      // (frames whose x axis is one launch -- small tiles -- have no such point: both copies follow the frame)
+        if (rq.after_b_recorded) {      // (frames whose x axis is one launch -- small tiles -- have no such point: both copies follow the frame)
             HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->nrm_final, 0));
             nst = c->copy_stream;
         }
@@ -1440,10 +1473,11 @@ int ocean_select_streams(ocean_t* c, uint32_t frames, float* us_per_frame)
     for (int k = 0; k < CAND; ++k) {
         std::swap(c->own[0], c->own[k]);                   // candidate k runs the serial path (chain 0's buffers)
         rc = OCEAN_OK;
-        for (int j = 0; j < 5 && !rc; ++j) rc = enqueue_frame(c, 0.25f * (float)j, false, nullptr);
+        FrameRequest serial;            // (defaults: not pipelined, not tracked)
+        for (int j = 0; j < 5 && !rc; ++j) { serial.t = 0.25f * (float)j; rc = enqueue_frame(c, serial); }
         hipError_t e = rc ? hipSuccess : hipStreamSynchronize(c->own[0]);
         if (!rc && e == hipSuccess) e = hipEventRecord(c->start_ev, c->own[0]);
-        for (uint32_t j = 0; j < frames && !rc && e == hipSuccess; ++j) rc = enqueue_frame(c, 0.25f * (float)j, false, nullptr);
+        for (uint32_t j = 0; j < frames && !rc && e == hipSuccess; ++j) { serial.t = 0.25f * (float)j; rc = enqueue_frame(c, serial); }
         if (!rc && e == hipSuccess) e = hipEventRecord(c->end_ev[0], c->own[0]);
         if (!rc && e == hipSuccess) e = hipEventSynchronize(c->end_ev[0]);
         float ms = 0.f;
@@ -1472,13 +1506,16 @@ int ocean_time_frames(ocean_t* c, float t0, float dt, int warmup, int frames, fl
     if (!c->prepared) return OCEAN_E_NOT_READY;
     HIP_TRY(hipSetDevice(c->device));
     int rc;
+    FrameRequest rq;
+    rq.pipelined = true;
+    auto frame = [&](int j, hipEvent_t* marks) { rq.t = t0 + dt * (float)j; rq.marks = marks; return enqueue_frame(c, rq); };
     for (int j = 0; j < warmup; ++j)
-        if ((rc = enqueue_frame(c, t0 + dt * (float)j, true, nullptr))) return rc;
+        if ((rc = frame(j, nullptr))) return rc;
     OCEAN_TRY(sync_all(c));
     HIP_TRY(hipEventRecord(c->start_ev, stream_of(c, 0)));
     HIP_TRY(hipEventSynchronize(c->start_ev));
     for (int j = 0; j < frames; ++j)
-        if ((rc = enqueue_frame(c, t0 + dt * (float)(warmup + j), true, nullptr))) return rc;
+        if ((rc = frame(warmup + j, nullptr))) return rc;
     // the two chains are independent: the timed region ends when the later one does
     const int nstreams = c->user ? 1 : MAXD;
     for (int i = 0; i < nstreams; ++i) HIP_TRY(hipEventRecord(c->end_ev[i], stream_of(c, i)));
@@ -1513,14 +1550,14 @@ int ocean_time_frames(ocean_t* c, float t0, float dt, int warmup, int frames, fl
         if (!pipe) {
             // serial frames: one frame at a time (least event-queueing overhead, ~2 us per launch)
             for (int j = 0; j < frames; ++j) {
-                if ((rc = enqueue_frame(c, t0 + dt * (float)(warmup + j), true, c->mark_ev[0]))) return rc;
+                if ((rc = frame(warmup + j, c->mark_ev[0]))) return rc;
                 if ((rc = collect(0))) return rc;
             }
         } else {
             for (int j = 0; j < frames; ++j) {
                 const int set = (int)(c->frame_ctr % (uint64_t)c->depth);
                 if (j >= nsets && (rc = collect(set))) return rc;
-                if ((rc = enqueue_frame(c, t0 + dt * (float)(warmup + j), true, c->mark_ev[set]))) return rc;
+                if ((rc = frame(warmup + j, c->mark_ev[set]))) return rc;
             }
             // the frames still in flight are the last min(frames, nsets) ones, oldest first
             const int outstanding = frames < nsets ? frames : nsets;

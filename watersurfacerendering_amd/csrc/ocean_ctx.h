@@ -130,7 +130,6 @@ struct ocean_ctx {
     unsigned* minmax[MAXD] = {};
     unsigned* zdone[MAXD] = {};     // [tiles] z-pass workgroups that have finished, counted up for ever (one-launch frames: FrameArgs::zdone)
     unsigned zgen[MAXD] = {};       // one-launch frames the chain has run (zdone's target = zgen x (N/2 + 1))
-    int cur_set = 0;                // the chain of the frame being enqueued (for the launcher)
     uint32_t attr_one_n = 0;        // tile size whose one-launch kernel had its LDS attribute set through this context
     unsigned* hdone[MAXD] = {};     // [tiles] HEIGHT workgroups of the chain's current frame that have finished (merged x pass: FrameArgs::hdone)
     uint4* done_rec[MAXD] = {};     // [tiles] host-coherent completion records (min key, max key, sequence, 0) written by the last
@@ -145,7 +144,6 @@ struct ocean_ctx {
     float last_t[MAXD] = {};        // time, regime (pipelined or not) and form of the chain's most recent frame: what recover_fault (ocean_api.hip) needs to
     bool last_pipe[MAXD] = {};      //   run it again
     bool last_handoff[MAXD] = {};   // ... it used an in-launch hand-off (merged x pass / one-launch frame: the only forms whose waits can give up)
-    bool handoff = false;           // set by launch_frame: the frame it has just enqueued uses an in-launch hand-off
     bool recovering = false;        // recover_fault is re-enqueueing (no recursion)
     int placement_override = 0;     // ocean_set_placement_search: 0 = the library's rule (OceanTuning), n >= 1 = that many candidates (1 = off)
     bool placement_done = false;        // the search has run (or was found unnecessary) for the buffers this context holds now
@@ -210,17 +208,12 @@ struct ocean_ctx {
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
     hipEvent_t mark_ev[MAXD][2 * OCEAN_MAX_LAUNCHES] = {};   // per-launch timing: (start, stop) of each launch of a frame
-    int launch_count = 3;               // launches of the most recent frame (3; 2 with the merged x pass, 1 in a one-launch frame) and the kernel (0 z pass, 1 k_xpass_b,
-    int launch_kernel[OCEAN_MAX_LAUNCHES] = {0, 1, 2};   //   2 k_xpass_disp) each of them ran: ocean_time_frames adds them up per kernel
-    ocean_launch_info last_launch[3] = {};  // what the most recent frame launched (ocean_last_launch)
+    int launch_count = 3;               // launches of the most recent successful frame (3; 2 with the merged x pass, 1 in a one-launch frame) and the kernel (0 z pass,
+    int launch_kernel[OCEAN_MAX_LAUNCHES] = {0, 1, 2};   //   1 k_xpass_b, 2 k_xpass_disp) each of them ran (copied from FrameLaunch by enqueue_frame): ocean_time_frames adds them up per kernel
+    ocean_launch_info last_launch[3] = {};  // what the most recent frame launched (ocean_last_launch; written by launch_frame)
     hipEvent_t z_done[MAXD] = {};       // pipelined frames right after a drain: recorded behind a chain's z pass (see enqueue_frame)
-    hipEvent_t after_z = nullptr;       // what launch_frame records behind the z pass of the frame being enqueued (null: nothing)
-    hipEvent_t after_b = nullptr;       // ... and behind k_xpass_b, where the frame has a displacement pass of its own behind it (ocean_compute_waves_read)
-    bool after_b_recorded = false;
     hipStream_t copy_stream = nullptr;  // ocean_compute_waves_read: the normal map's device-to-host copy runs here, beside the displacement pass
     hipEvent_t nrm_final = nullptr, copy_done[2] = {};   // its events: normal map final / the two copies have landed
-    float4* host_out[2] = {};           // set around its enqueue: device addresses of the caller's page-locked (displacement, normal) arrays when the
-                                        //   x passes are to store the maps there themselves (FrameArgs::disp_host / nrm_host), null otherwise
     int burst_pos = 0;                  // pipelined frames enqueued since the context's streams were last drained
     int z_last_set = -1;
     hipEvent_t consumer_ev = nullptr;   // behind the most recent consumer launch (mips, grid): the context-wide output buffers of
@@ -280,12 +273,39 @@ int check_fault(ocean_ctx* c);      // only that recovery, where one is due (bef
 // tile size -- staging, foam -- and the "ready" state of what does not; true (ocean_destroy): the grid, the mips and the consumer event as well.
 void ocean_consumers_release(ocean_ctx* c, bool everything);
 
-// One frame = three launches on `st` (ocean_launch.h); one entry point per group of tile sizes, each compiled in its
-// own translation unit (frames_*.hip) so that the library builds in parallel.  stream_maps: bit 0 normal map and
-// bit 1 displacement map stored non-temporally, bit 2 intermediates stored non-temporally, bit 3 half2 intermediates,
-// bit 4 the frame runs alone on the device (serial frames: the z pass may split its last round of columns).
-// marks: 2 x OCEAN_MAX_LAUNCHES events (start, stop per launch) or null.
-hipError_t ocean_launch_frame_small(ocean_ctx* c, const ocean::FrameArgs& a, int stream_maps, hipStream_t st, hipEvent_t* marks);   // 16 .. 256
-hipError_t ocean_launch_frame_mid(ocean_ctx* c, const ocean::FrameArgs& a, int stream_maps, hipStream_t st, hipEvent_t* marks);     // 512, 1024
-hipError_t ocean_launch_frame_2048(ocean_ctx* c, const ocean::FrameArgs& a, int stream_maps, hipStream_t st, hipEvent_t* marks);
-hipError_t ocean_launch_frame_4096(ocean_ctx* c, const ocean::FrameArgs& a, int stream_maps, hipStream_t st, hipEvent_t* marks);
+// ---- what crosses between ocean_api.hip and the frame launchers (frames_*.hip, ocean_launch.h) ----------------------------------------------
+// How one frame stores what it writes, which form its intermediates take and what it shares the device with: decided per frame by
+// enqueue_frame (ocean_api.hip, where the measurements behind each rule are), read by launch_frame.
+struct FramePolicy {
+    bool nt_normal = false;     // the normal map ...
+    bool nt_disp = false;       // ... and the displacement map are stored non-temporally: written once, never re-read by the pipeline
+    bool nt_inter = false;      // the intermediates are stored non-temporally too (pipelined frames whose chains outgrow the memory-side cache); the z
+                                //   pass then takes two columns per workgroup where that form exists, so that the streamed stores cover whole lines
+    bool half_inter = false;    // half2 intermediates (ocean_set_intermediate_precision): a kernel variant, not a store policy
+    bool alone = false;         // the frame has the device to itself (a serial frame): which staggered start, which sizes merge their x pass,
+                                //   write-through intermediates; never a one-launch frame
+};
+
+// One call of the launcher: what it is given beside the kernels' own argument block, and what it reports back.  Nothing of this outlives the
+// call: enqueue_frame builds one per frame and commits the results of a successful one to the context.
+struct FrameLaunch {
+    // in
+    FramePolicy policy;
+    int set = 0;                        // the frame's chain
+    hipStream_t stream = nullptr;
+    hipEvent_t* marks = nullptr;        // 2 x OCEAN_MAX_LAUNCHES events (start, stop per launch) or null
+    hipEvent_t after_z = nullptr;       // recorded behind the z pass (null: nothing)
+    hipEvent_t after_b = nullptr;       // ... and behind k_xpass_b, where the frame has a displacement pass of its own behind it
+    // out
+    bool after_b_recorded = false;      // (frames whose x axis is one launch have no such point)
+    bool handoff = false;               // the frame uses an in-launch hand-off (merged x pass / one-launch frame)
+    int launch_count = 0;               // launches of the frame: 3; 2 with the merged x pass, 1 in a one-launch frame ...
+    int launch_kernel[OCEAN_MAX_LAUNCHES] = {};     // ... and the kernel each of them ran (0 z pass, 1 k_xpass_b, 2 k_xpass_disp)
+};
+
+// One frame = one to three launches on fl.stream (ocean_launch.h); one entry point per group of tile sizes, each compiled in its own
+// translation unit (frames_*.hip) so that the library builds in parallel.
+hipError_t ocean_launch_frame_small(ocean_ctx* c, const ocean::FrameArgs& a, FrameLaunch& fl);  // 16 .. 256
+hipError_t ocean_launch_frame_mid(ocean_ctx* c, const ocean::FrameArgs& a, FrameLaunch& fl);    // 512, 1024
+hipError_t ocean_launch_frame_2048(ocean_ctx* c, const ocean::FrameArgs& a, FrameLaunch& fl);
+hipError_t ocean_launch_frame_4096(ocean_ctx* c, const ocean::FrameArgs& a, FrameLaunch& fl);

@@ -1062,14 +1062,14 @@ __global__ void __launch_bounds__(T, (zpass_c1_min_waves<N, T, FAST>())) k_zpass
 }
 // tile sizes whose z pass has the single-transform form (the launcher picks it where it is faster: ocean_launch.h)
 template <int N> constexpr bool zpass_has_c1() { return N >= 1024; }
-// Where the single-transform form is the faster one (profiles/r04_zpass_experiments.txt; stream_maps: ocean_ctx.h, bit 2 = streamed
+// Where the single-transform form is the faster one (profiles/r04_zpass_experiments.txt; nt_inter: FramePolicy, ocean_ctx.h -- streamed
 // intermediates): 4096^2 always (three workgroups per CU instead of one: z pass 111 -> 95 us); 2048^2 and batches of 1024^2 with plain
 // intermediate stores (2048^2 24.4 -> 23.2 us and no split last round, 8 x 1024^2 38.1 -> 33.9); a lone 1024^2 tile keeps the
 // two-transform form (half the dependent chain: 14.3 vs 15.2 us), streamed intermediates below 4096 the two-column form (whole-line stores).
-template <int N> inline bool zpass_c1_pays(int stream_maps, unsigned tiles)
+template <int N> inline bool zpass_c1_pays(bool nt_inter, unsigned tiles)
 {
     if (N == 4096) return true;
-    if (stream_maps & 4) return false;
+    if (nt_inter) return false;
     return N == 2048 || tiles >= 2;
 }
 

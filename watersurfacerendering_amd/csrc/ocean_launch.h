@@ -1,4 +1,4 @@
-// ocean_launch.h -- launch_frame<N>: the three launches of one frame at tile size N (included by frames_*.hip).
+// ocean_launch.h -- launch_frame<N>: the launches of one frame at tile size N, three at most (included by frames_*.hip).
 #pragma once
 #include <cstdlib>
 
@@ -29,9 +29,10 @@ static void launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, 
 template <int N> constexpr bool xmerge_pays(bool alone) { return alone ? N <= 128 : N <= 512; }
 
 template <int N>
-static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps /* bit 0: normal map, bit 1: displacement map, bit 2: intermediates */,
-                               hipStream_t st, hipEvent_t* marks /* 2 x OCEAN_MAX_LAUNCHES events (start, stop per launch) or null */)
+static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl)
 {
+    const FramePolicy& p = fl.policy;
+    const hipStream_t st = fl.stream;
     using G = Geo<N>;
     using HF = Half<N>;
     const unsigned tiles = c->tiles;
@@ -45,7 +46,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
     static_assert(HF::NUP % (2 * C) == 0, "height row blocks");
     constexpr unsigned hb_b = xpass_height_groups<N, C>(), nb = (HF::NU + C - 1) / C;
     const bool fast = !a.h0h && a.omega_q;       // the usual form of the spectrum: fp32 h0, 16-bit dispersion
-    const bool alone = (stream_maps & 16) != 0;
+    const bool alone = p.alone;
     const unsigned cus = (unsigned)(c->cu_count > 0 ? c->cu_count : 0);
     // Staggered start (ocean_kernels.h: start_ramp_wait; the rule and its constants: OceanTuning, ocean_ctx.h).  A launch gets one when its WHOLE
     // grid is resident at once on this device -- grid <= compute units x resident workgroups per unit, the latter asked of the runtime for the
@@ -78,18 +79,16 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
         OCEAN_ALLOW_Z2(true) OCEAN_ALLOW_Z2(false)
 #undef OCEAN_ALLOW_Z2
 #undef OCEAN_ALLOW_Z
-#define OCEAN_ALLOW_X(kern, lds) \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, false, false, false>, lds)) != hipSuccess) return e; \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, true, false, false>, lds)) != hipSuccess) return e;  \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, false, true, false>, lds)) != hipSuccess) return e;  \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, true, true, false>, lds)) != hipSuccess) return e;   \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, false, false, true>, lds)) != hipSuccess) return e;  \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, true, false, true>, lds)) != hipSuccess) return e;   \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, false, true, true>, lds)) != hipSuccess) return e;   \
-        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, true, true, true>, lds)) != hipSuccess) return e;
+#define OCEAN_ALLOW_X1(kern, lds, z16, jac) \
+        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, false, z16, jac>, lds)) != hipSuccess) return e; \
+        if ((e = allow_lds(kern<N, C, G::T_C, typename G::PC, true, z16, jac>, lds)) != hipSuccess) return e;
+#define OCEAN_ALLOW_X2(kern, lds, jac) OCEAN_ALLOW_X1(kern, lds, false, jac) OCEAN_ALLOW_X1(kern, lds, true, jac)
+#define OCEAN_ALLOW_X(kern, lds) OCEAN_ALLOW_X2(kern, lds, false) OCEAN_ALLOW_X2(kern, lds, true)
         OCEAN_ALLOW_X(k_xpass_b, lds_b)
         OCEAN_ALLOW_X(k_xpass_disp, lds_m)
 #undef OCEAN_ALLOW_X
+#undef OCEAN_ALLOW_X2
+#undef OCEAN_ALLOW_X1
         c->attr_n = (uint32_t)N;
     }
     if (c->start_ramp && cus) {
@@ -107,7 +106,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
             c->occ_z = oz; c->occ_z_all = oza; c->occ_b = ob; c->occ_d = od; c->occ_n = N;
         }
         int bpt[3];
-        ocean_launch_bytes_per_texel((stream_maps & 8) != 0, a.mode == 3, a.h0h != nullptr, a.omega_q != nullptr, bpt);
+        ocean_launch_bytes_per_texel(p.half_inter, a.mode == 3, a.h0h != nullptr, a.omega_q != nullptr, bpt);
         const OceanTuning& tu = c->tune;
         const double texels = (double)tiles * N * N;
         auto ramp_ticks = [&](int bytes_per_texel, unsigned workgroups, int per_cu, double scale) -> int {
@@ -124,11 +123,11 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
     }
     // the form of the z pass (see above); the usual form of the spectrum (fp32 h0, 16-bit dispersion) has instantiations without the
     // other forms' code (FAST)
-    bool c1 = HASC1 && zpass_c1_pays<N>(stream_maps, tiles);
-    bool zw2 = HAS2 && !c1 && (stream_maps & 4);
+    bool c1 = HASC1 && zpass_c1_pays<N>(p.nt_inter, tiles);
+    bool zw2 = HAS2 && !c1 && p.nt_inter;
     // a SERIAL frame's fp32 intermediates go out write-through where that form exists (ocean_kernels.h: store_z, zpass_has_wt)
     constexpr bool HAS_WT = HASC1 && zpass_has_wt<N>();
-    const bool wt_frame = HAS_WT && alone && !(stream_maps & (4 | 8)) && c->z_write_through;
+    const bool wt_frame = HAS_WT && alone && !p.nt_inter && !p.half_inter && c->z_write_through;
     bool z_wt = c1 && wt_frame;
     // Frame order: z pass (four transforms per column) -> k_xpass_b (HEIGHT + NORMAL workgroups) -> k_xpass_disp.  (Round 5 also ran a SPLIT
     // order -- z pass {height, pair 0} -> HEIGHT workgroups -> k_xpass_disp -> z pass {pair 1, pair 2} -> NORMAL workgroups: bit-identical, slower
@@ -151,9 +150,10 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
     // 512^2 11.6-12.3 / 7.7 / 18.6: from 256^2 up the z pass's 8-byte write-through stores and the x-axis workgroups' reads past the L2 cost more
     // than the launch they save (profiles/r05_small_tile_experiments.txt), so those sizes keep the merged x pass.
     constexpr bool HAS_ONE = (N <= 128 || (DEV && N <= 512)) && G::T_ROWS == G::T_C;      // (developer builds: up to 512^2, for the A/B of that log)
+    // (fp32 intermediates and never the Jacobian mode: the one-launch records of ocean_last_launch, below, rely on `describe` adding neither flag)
     // (like the merged x pass only where every workgroup of the grid has a slot at once -- one per compute unit, the regime the hand-off recipe is
     //  measured for: forward progress then never depends on the order in which workgroups are dispatched)
-    bool one_launch = HAS_ONE && !alone && tiles == 1 && a.mode <= 2 && fast && (stream_maps & 15) == 3 && c->merged_x &&
+    bool one_launch = HAS_ONE && !alone && tiles == 1 && a.mode <= 2 && fast && p.nt_normal && p.nt_disp && !p.nt_inter && !p.half_inter && c->merged_x &&
                       ((unsigned)(N / 2 + 1) + hb_b + 2u * nb) <= c->tune.handoff_wg_per_cu * cus;
     // the DISP workgroups of a merged launch poll the HEIGHT count; beside other chains' launches a poll every ~3 us instead of back to back
     // takes the pollers off the memory system (512^2 depth 4: 7.66-7.97 -> 7.35-7.55 us per frame, 256^2 7.8-9.7 -> 7.2-7.3); a serial frame
@@ -162,7 +162,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
 #ifdef OCEAN_DEVELOPER      // A/B builds only: the shipped library reads no environment.  Every override of the rules above, in their order
     {   static const char* const c1_env = getenv("OCEAN_ZC1");                  // 0 / 1
         if (c1_env && HASC1) c1 = atoi(c1_env) != 0;
-        zw2 = HAS2 && !c1 && (stream_maps & 4);
+        zw2 = HAS2 && !c1 && p.nt_inter;
         static const char* const zw_env = getenv("OCEAN_ZW");                   // 1 or 2
         if (zw_env && HAS2 && !c1) zw2 = atoi(zw_env) == 2;
         const char* const wt_env = getenv("OCEAN_Z_WT");          // 0: off (read per frame: A/B inside one process)
@@ -180,13 +180,20 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
         if (rb && on) ramp_b = atoi(rb);
         if (rd && on) ramp_d = atoi(rd); }
 #endif
-    c->handoff = merged_x || one_launch;      // (what recover_fault re-runs without a hand-off, should one of this frame's in-launch waits give up)
-    int launches = 0;
+    fl.handoff = merged_x || one_launch;      // (what recover_fault re-runs without a hand-off, should one of this frame's in-launch waits give up)
+    fl.launch_count = 0;
     auto next_marks = [&](int kernel) -> hipEvent_t* {      // the event pair of the frame's next launch; remembers which kernel it times
-        c->launch_kernel[launches] = kernel;
-        hipEvent_t* m = marks ? marks + 2 * launches : nullptr;
-        ++launches;
-        return m;
+        const int l = fl.launch_count++;
+        fl.launch_kernel[l] = kernel;
+        return fl.marks ? fl.marks + 2 * l : nullptr;
+    };
+    // what ocean_last_launch reports of launch idx: the caller passes what differs between the launches, the flags of the frame's form are added here
+    auto describe = [&](int idx, unsigned grid_x, unsigned block, unsigned per_workgroup, size_t lds, uint32_t flags) {
+        ocean_launch_info& li = c->last_launch[idx];
+        li.tile_size = N; li.grid_x = grid_x; li.grid_y = tiles; li.block = block; li.mode = (uint32_t)a.mode;
+        li.per_workgroup = per_workgroup;
+        li.lds_bytes = (uint32_t)lds;
+        li.flags = flags | (p.half_inter ? OCEAN_LAUNCH_HALF_INTER : 0u) | (a.mode == 3 ? OCEAN_LAUNCH_JACOBIAN : 0u);
     };
     const int rec_last = a.rec_mode;                         // what the frame's LAST launch does with the completion records (ocean_api.hip)
     auto launch_z = [&]() -> hipError_t {
@@ -198,16 +205,10 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
         const unsigned threads = c1 ? (unsigned)zpass_c1_threads<N>() : (unsigned)G::T_ROWS;
         const size_t lds = c1 ? zpass_c1_lds_bytes<N>() : (zw2 ? lds_rows2 : lds_rows);
         const dim3 grid(gx, tiles), block(threads);
-        {
-            ocean_launch_info& li = c->last_launch[0];
-            li.tile_size = N; li.grid_x = gx; li.grid_y = tiles; li.block = threads; li.mode = (uint32_t)a.mode;
-            li.per_workgroup = zw2 ? 2u : 1u;
-            li.lds_bytes = (uint32_t)lds;
-            li.flags = ((stream_maps & 4) ? OCEAN_LAUNCH_NT_INTER : 0u) | ((stream_maps & 8) ? OCEAN_LAUNCH_HALF_INTER : 0u) |
-                       (a.mode == 3 ? OCEAN_LAUNCH_JACOBIAN : 0u) | (a.h0h ? OCEAN_LAUNCH_FP16_SPECTRUM : 0u) |
-                       (a.omega_q ? 0u : OCEAN_LAUNCH_FP32_DISPERSION) | (c1 ? OCEAN_LAUNCH_SINGLE_TRANSFORM : 0u) |
-                       (za.start_ramp ? OCEAN_LAUNCH_STAGGERED_START : 0u) | (z_wt ? OCEAN_LAUNCH_WT_INTER : 0u);
-        }
+        describe(0, gx, threads, zw2 ? 2u : 1u, lds,
+                 (p.nt_inter ? OCEAN_LAUNCH_NT_INTER : 0u) | (a.h0h ? OCEAN_LAUNCH_FP16_SPECTRUM : 0u) |
+                 (a.omega_q ? 0u : OCEAN_LAUNCH_FP32_DISPERSION) | (c1 ? OCEAN_LAUNCH_SINGLE_TRANSFORM : 0u) |
+                 (za.start_ramp ? OCEAN_LAUNCH_STAGGERED_START : 0u) | (z_wt ? OCEAN_LAUNCH_WT_INTER : 0u));
         hipEvent_t* mz = next_marks(0);
 #ifdef OCEAN_CLOCKPROBE
         {   // diagnostic: this translation unit's copy of the probe pointer, set when the context's buffer changes (not per frame)
@@ -230,8 +231,8 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
 #define OCEAN_ZPASS2(znt, z16) \
         do { if (fast) OCEAN_ZPASS3(znt, z16, true); else OCEAN_ZPASS3(znt, z16, false); } while (0)
 #define OCEAN_ZPASS(znt) \
-        do { if (stream_maps & 8) OCEAN_ZPASS2(znt, true); else OCEAN_ZPASS2(znt, false); } while (0)
-        if (stream_maps & 4) OCEAN_ZPASS(true); else OCEAN_ZPASS(false);
+        do { if (p.half_inter) OCEAN_ZPASS2(znt, true); else OCEAN_ZPASS2(znt, false); } while (0)
+        if (p.nt_inter) OCEAN_ZPASS(true); else OCEAN_ZPASS(false);
 #undef OCEAN_ZPASS
 #undef OCEAN_ZPASS2
 #undef OCEAN_ZPASS3
@@ -245,46 +246,30 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
         do { if (jac) launch(kern<N, C, G::T_C, typename G::PC, nts, z16, true>, grid, blk, lds, st, ev, args);       \
              else launch(kern<N, C, G::T_C, typename G::PC, nts, z16, false>, grid, blk, lds, st, ev, args); } while (0)
 #define OCEAN_XPASS(kern, grid, lds, ev, nts, args)                                                                 \
-        do { if (stream_maps & 8) OCEAN_XPASS2(kern, grid, lds, ev, nts, true, args);                                 \
+        do { if (p.half_inter) OCEAN_XPASS2(kern, grid, lds, ev, nts, true, args);                                  \
              else OCEAN_XPASS2(kern, grid, lds, ev, nts, false, args); } while (0)
     auto launch_xb = [&](bool merged) {      // HEIGHT + NORMAL workgroups; merged: the DISP workgroups as well -- then the frame's last launch
         const dim3 gb(hb + nb + (merged ? nb : 0u), tiles);
-        {
-            ocean_launch_info& li = c->last_launch[1];
-            li.tile_size = N; li.grid_x = gb.x; li.grid_y = tiles; li.block = G::T_C; li.mode = (uint32_t)a.mode;
-            li.per_workgroup = C;
-            li.lds_bytes = (uint32_t)lds_b;
-            li.flags = ((stream_maps & 1) ? OCEAN_LAUNCH_NT_MAPS : 0u) | ((stream_maps & 8) ? OCEAN_LAUNCH_HALF_INTER : 0u) |
-                       (jac ? OCEAN_LAUNCH_JACOBIAN : 0u) | (ramp_b ? OCEAN_LAUNCH_STAGGERED_START : 0u) |
-                       (merged ? OCEAN_LAUNCH_MERGED_X : 0u);
-            if (merged) {                        // no k_xpass_disp this frame: its record describes the launch that did its work
-                c->last_launch[2] = li;
-                c->last_launch[2].flags = (li.flags & ~(uint32_t)OCEAN_LAUNCH_NT_MAPS) | ((stream_maps & 2) ? OCEAN_LAUNCH_NT_MAPS : 0u);
-            }
-        }
+        const uint32_t flags_b = (ramp_b ? OCEAN_LAUNCH_STAGGERED_START : 0u) | (merged ? OCEAN_LAUNCH_MERGED_X : 0u);
+        describe(1, gb.x, G::T_C, C, lds_b, flags_b | (p.nt_normal ? OCEAN_LAUNCH_NT_MAPS : 0u));
+        // no k_xpass_disp this frame: its record describes the launch that did its work
+        if (merged) describe(2, gb.x, G::T_C, C, lds_b, flags_b | (p.nt_disp ? OCEAN_LAUNCH_NT_MAPS : 0u));
         hipEvent_t* mb = next_marks(1);
         FrameArgs ba = a;
         ba.xb_roles = merged ? 7 : 3; ba.rec_mode = merged ? rec_last : 0;
         ba.poll_sleep = poll_sleep;
         ba.start_ramp = ramp_b;             // over its normal-map workgroups (the height workgroups start at once)
-        if (stream_maps & 1) OCEAN_XPASS(k_xpass_b, gb, lds_b, mb, true, ba);
+        if (p.nt_normal) OCEAN_XPASS(k_xpass_b, gb, lds_b, mb, true, ba);
         else OCEAN_XPASS(k_xpass_b, gb, lds_b, mb, false, ba);
     };
     auto launch_xd = [&]() {
         const dim3 gd(nb, tiles);
-        {
-            ocean_launch_info& li = c->last_launch[2];
-            li.tile_size = N; li.grid_x = gd.x; li.grid_y = tiles; li.block = G::T_C; li.mode = (uint32_t)a.mode;
-            li.per_workgroup = C;
-            li.lds_bytes = (uint32_t)lds_m;
-            li.flags = ((stream_maps & 2) ? OCEAN_LAUNCH_NT_MAPS : 0u) | ((stream_maps & 8) ? OCEAN_LAUNCH_HALF_INTER : 0u) |
-                       (jac ? OCEAN_LAUNCH_JACOBIAN : 0u) | (ramp_d ? OCEAN_LAUNCH_STAGGERED_START : 0u);
-        }
+        describe(2, gd.x, G::T_C, C, lds_m, (p.nt_disp ? OCEAN_LAUNCH_NT_MAPS : 0u) | (ramp_d ? OCEAN_LAUNCH_STAGGERED_START : 0u));
         hipEvent_t* md = next_marks(2);
         FrameArgs da = a;
         da.rec_mode = rec_last;
         da.start_ramp = ramp_d;             // its 257 workgroups are one per CU: the same read-then-write burst
-        if (stream_maps & 2) OCEAN_XPASS(k_xpass_disp, gd, lds_m, md, true, da);
+        if (p.nt_disp) OCEAN_XPASS(k_xpass_disp, gd, lds_m, md, true, da);
         else OCEAN_XPASS(k_xpass_disp, gd, lds_m, md, false, da);
     };
     if constexpr (HAS_ONE) {
@@ -297,35 +282,29 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, int stream_maps
             }
             FrameArgs fa = a;
             fa.xb_roles = 7; fa.rec_mode = rec_last; fa.start_ramp = 0;
-            fa.zdone_target = (++c->zgen[c->cur_set]) * (unsigned)(N / 2 + 1);
+            fa.zdone_target = (++c->zgen[fl.set]) * (unsigned)(N / 2 + 1);
             fa.poll_sleep = poll_sleep;
             const dim3 grid((N / 2 + 1) + hb_b + 2 * nb, tiles), block(G::T_C);
-            for (int k = 0; k < 3; ++k) {
-                ocean_launch_info& li = c->last_launch[k];
-                li.tile_size = N; li.grid_x = grid.x; li.grid_y = tiles; li.block = G::T_C; li.mode = (uint32_t)a.mode;
-                li.per_workgroup = k == 0 ? 1u : (uint32_t)C;
-                li.lds_bytes = (uint32_t)lds_one;
-                li.flags = OCEAN_LAUNCH_ONE_LAUNCH | (k == 0 ? 0u : (OCEAN_LAUNCH_NT_MAPS | OCEAN_LAUNCH_MERGED_X));
-            }
+            // (describe adds nothing: the one_launch rule above excludes half2 intermediates and the Jacobian mode)
+            for (int k = 0; k < 3; ++k)
+                describe(k, grid.x, G::T_C, k == 0 ? 1u : (unsigned)C, lds_one, OCEAN_LAUNCH_ONE_LAUNCH | (k == 0 ? 0u : (OCEAN_LAUNCH_NT_MAPS | OCEAN_LAUNCH_MERGED_X)));
             launch(kern, grid, block, lds_one, st, next_marks(0), fa);
-            if (c->after_z && (e = hipEventRecord(c->after_z, st)) != hipSuccess) return e;
-            c->launch_count = launches;
+            if (fl.after_z && (e = hipEventRecord(fl.after_z, st)) != hipSuccess) return e;
             return hipGetLastError();
         }
     }
     if ((e = launch_z()) != hipSuccess) return e;
-    if (c->after_z && (e = hipEventRecord(c->after_z, st)) != hipSuccess) return e;   // the first frames after a drain: the next chain's z pass starts behind this one (ocean_api.hip)
+    if (fl.after_z && (e = hipEventRecord(fl.after_z, st)) != hipSuccess) return e;   // the first frames after a drain: the next chain's z pass starts behind this one (ocean_api.hip)
     if (merged_x) {
         launch_xb(true);
     } else {
         launch_xb(false);
         // the normal map is final behind this launch: ocean_compute_waves_read starts its device-to-host copy here, beside the displacement pass
-        if (c->after_b) { if ((e = hipEventRecord(c->after_b, st)) != hipSuccess) return e; c->after_b_recorded = true; }
+        if (fl.after_b) { if ((e = hipEventRecord(fl.after_b, st)) != hipSuccess) return e; fl.after_b_recorded = true; }
         launch_xd();
     }
 #undef OCEAN_XPASS2
 #undef OCEAN_XPASS
-    c->launch_count = launches;
     return hipGetLastError();
 }
 
