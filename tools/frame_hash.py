@@ -1,6 +1,7 @@
 """Hash of both maps (+ heights) of a few frames of one configuration: bit-identity checks between kernel variants
 (developer builds: the variant is picked by environment switches such as OCEAN_ZPERS, read by libocean_hip_<name>.so).
-usage: [OCEAN_HIP_LIB=...] python tools/frame_hash.py N [tiles] [depth] [mode] [inter_bits]"""
+usage: [OCEAN_HIP_LIB=...] python tools/frame_hash.py N [tiles] [depth] [mode] [inter_bits] [h0_bits] [anim_period]
+(h0_bits 16: the fp16 spectrum; anim_period 4.0e5: dispersion multiples beyond 16 bits, i.e. the fp32 dispersion array)"""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import devlib  # noqa: F401
@@ -8,8 +9,10 @@ import numpy as np
 import watersurfacerendering_amd as W
 n = int(sys.argv[1]); tiles = int(sys.argv[2]) if len(sys.argv) > 2 else 1; depth = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 mode = int(sys.argv[4]) if len(sys.argv) > 4 else 0; bits = int(sys.argv[5]) if len(sys.argv) > 5 else 32
+h0_bits = int(sys.argv[6]) if len(sys.argv) > 6 else 32; period = float(sys.argv[7]) if len(sys.argv) > 7 else None
 b = W.OceanBatch(n, tiles, 0)
-b.set_mode(mode); b.set_intermediate_precision(bits); b.set_pipeline_depth(depth)
+if period is not None: b.set_params(anim_period=period)
+b.set_mode(mode); b.set_intermediate_precision(bits); b.set_spectrum_precision(h0_bits); b.set_pipeline_depth(depth)
 b.prepare(0x5EED0000)
 h = hashlib.sha256()
 for t in (0.0, 1.7, 1234.5):
@@ -19,5 +22,5 @@ for t in (0.0, 1.7, 1234.5):
     d, q = b.read_maps()
     h.update(d.tobytes()); h.update(q.tobytes()); h.update(np.asarray(b.heights(0), dtype=np.float32).tobytes())
 z = b.last_launch()[0]
-print(f"N={n}x{tiles} depth={depth} mode={mode} bits={bits} zpass grid={z['grid_x']}x{z['grid_y']} flags={z['flags']} per_wg={z['per_workgroup']}  sha={h.hexdigest()[:20]}")
+print(f"N={n}x{tiles} depth={depth} mode={mode} bits={bits} h0_bits={h0_bits} period={period} zpass grid={z['grid_x']}x{z['grid_y']} flags={z['flags']} per_wg={z['per_workgroup']}  sha={h.hexdigest()[:20]}")
 b.close()

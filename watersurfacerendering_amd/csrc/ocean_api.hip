@@ -776,7 +776,8 @@ static int enqueue_frame(ocean_ctx* c, FrameRequest& rq)
     a.mode = c->mode;
     a.start_ramp = 0;       // (set per launch by the launcher where a staggered start pays: ocean_launch.h)
     a.disp_host = rq.host_disp; a.nrm_host = rq.host_nrm;           // (ocean_compute_waves_read, small maps; null otherwise)
-    a.zmask = 15; a.xb_roles = 3;                   // (every transform in the one z pass; the x-axis roles per launch: ocean_launch.h)
+    a.zmask = 15;                                   // (FrameArgs::zmask: always all four transforms)
+    a.xb_disp = 0;                                  // (whether k_xpass_b carries the DISP workgroups: per launch, ocean_launch.h)
     a.xcd_rot = 0;
 #ifdef OCEAN_DEVELOPER
     if (const char* xr = getenv("OCEAN_XCD_ROT")) a.xcd_rot = atoi(xr) % 7;      // (read per frame: tools/slow_window.py flips it between windows)

@@ -186,7 +186,7 @@ struct FrameArgs {
     unsigned* fault;         // [1] host-coherent: set to 1 by an in-launch wait that gave up after 20 ms (the frame is then wrong: the host reports it)
     int poll_sleep;          //                  in-launch waits: s_sleep 127 (about 3.4 us of a 2.4 GHz clock / 64) repeated this many times between two polls of a counter (0: s_sleep 2)
     unsigned* hdone;         // [tiles]          HEIGHT workgroups of the frame that have finished (reset by the z pass): what the DISP workgroups
-                             //                  of a merged x pass wait for (k_xpass_b, xb_roles bit 2)
+                             //                  of a merged x pass wait for (k_xpass_b, xb_disp)
     uint4* done_rec;         // [tiles]          host-coherent completion records (min key, max key, frame_seq, 0), written by the
                              //                  displacement pass's last workgroup (frame_done)
     unsigned* done_ctr;      // [1]              workgroups of the displacement pass that have finished (the last one resets it)
@@ -202,11 +202,11 @@ struct FrameArgs {
     int mode;                // 0 FULL7 (reference), 1 CHOPPY5 (dDx/dx = dDz/dz = 0), 2 HEIGHT1 (height only),
                              // 3 JACOBIAN (FULL7 + the cross derivative; displacement.w = Jacobian of the horizontal displacement)
     // ---- set per launch by ocean_launch.h (ocean_api.hip leaves the defaults) ----
-    int zmask;               // z pass: the transforms this launch runs -- bit 0 pair 0, bit 1 pair 1, bit 2 pair 2, bit 3 the height (pair 3 in the
-                             // Jacobian mode).  The host always passes 15 = all (one z pass per frame); round 5's split frame order ran {height, pair 0} and
-                             // {pair 1, pair 2} as two launches, each animating the spectrum for itself (profiles/r05_4096_experiments.txt)
-    int xb_roles;            // k_xpass_b: bit 0 the HEIGHT workgroups, bit 1 the NORMAL workgroups (3 = both in one launch), bit 2 the DISP
-                             // workgroups as well (7 = the merged x pass: the whole x axis in one launch, no k_xpass_disp)
+    int zmask;               // always 15.  What is left of round 5's split frame order (one z pass ran some of a column's four transforms): k_zpass_c1
+                             // still tests its bits around its four batches.  The tests are always true, but they keep the compiler from scheduling
+                             // one batch into the next; that kernel stays as it was (see zpass_single_transforms)
+    int xb_disp;             // k_xpass_b: its HEIGHT and NORMAL workgroups are followed by the DISP workgroups (the merged x pass: the whole x axis in
+                             // one launch, no k_xpass_disp); 0: HEIGHT and NORMAL only
     int xcd_rot;             // developer builds only (OCEAN_XCD_ROT, tools/slow_window.py): the single-transform z pass hands the column groups of XCDs 1..7 round
                              // by this many places -- which XCD writes which part of the intermediates -- 0 in the shipped library
     float4* disp_host;       // [tiles][N][N] or null: the caller's page-locked destinations of ocean_compute_waves_read (device addresses): the x passes
@@ -352,6 +352,53 @@ __device__ __forceinline__ void animate_with_mirror(float2 h0a, float2 h0b, floa
     av = height_re(h0a.x, h0a.y, c, s);
     bv = height_re(h0b.x, h0b.y, c, s);
 }
+// Phase 1 of every z-pass form: animate columns nb .. nb + COLS - 1, each with its mirror, into the S+ tables sp[c * N + e], and leave
+// S-(0) of column c (Tz at e == 0) in raw[c] -- the head of the FFT image, not in use until the first exchange.  S- along the whole column
+// is needed by the Nyquist column nb == 0 only (Tx = S-); it pairs with itself, S+ is even and S- odd along e, so there ONE array G(e) =
+// h~(e, 0) carries both and sp holds G (one-column forms; the two-column form never gets column 0).  KZ_LDS: the kz table goes to LDS too
+// (kzt; the forms whose first stage reads kz from registers pass none).  Items in flight per thread: four (ten registers each), two for two
+// columns (four spill under 2048's cap); all of their loads issue ahead of the first sincos.
+template <int N, int T, int COLS, bool KZ_LDS, bool ZNT, bool FAST>
+__device__ __forceinline__ void zpass_phase1(const FrameArgs& a, int tile, int nb, int tid, float* sp, float* kzt, float* raw)
+{
+    const float t = a.t + (a.toff ? a.toff[tile] : 0.0f);
+    const float* __restrict__ k1 = a.k1d + (size_t)tile * N;               // [N], cache-resident table
+    const bool col0 = COLS == 1 && nb == 0;
+    const float h16s = a.h0h ? a.h0_inv_scale[tile] : 1.0f;
+    const float base = a.omega_q ? a.base_freq[tile] : 0.0f;
+    spectrum_form<FAST>(a, [&](auto h16, auto w16) {
+        constexpr bool H16 = decltype(h16)::value, W16 = decltype(w16)::value;
+        constexpr int PAIRS = N / 2, ITEMS = COLS * PAIRS;       // element pairs of a column, of the workgroup
+        constexpr int P1 = (ITEMS + T - 1) / T;
+        constexpr int PB = P1 > (COLS == 1 ? 4 : 2) ? (COLS == 1 ? 4 : 2) : P1;
+        constexpr bool GUARD = ITEMS % T != 0;
+        static_assert(P1 % PB == 0, "phase-1 batches");
+#pragma unroll 1
+        for (int ub = 0; ub < P1; ub += PB) {
+            float4 ha[PB];
+            float2 hb0[PB], hb1[PB], wv[PB];
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                const int it = tid + (ub + u) * T;
+                const int c = COLS == 1 ? 0 : it / PAIRS, n = 2 * (COLS == 1 ? it : it % PAIRS);
+                if (!GUARD || it < ITEMS) zpass_load_pair<N, H16, W16, ZNT>(a, tile, nb + c, n, h16s, base, ha[u], hb0[u], hb1[u], wv[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                const int it = tid + (ub + u) * T;
+                const int c = COLS == 1 ? 0 : it / PAIRS, n = 2 * (COLS == 1 ? it : it % PAIRS);
+                if (!GUARD || it < ITEMS) {
+                    float a0, b0, a1, b1;
+                    animate_with_mirror(make_float2(ha[u].x, ha[u].y), hb0[u], wv[u].x, t, a0, b0);
+                    animate_with_mirror(make_float2(ha[u].z, ha[u].w), hb1[u], wv[u].y, t, a1, b1);
+                    *reinterpret_cast<float2*>((c ? sp + N : sp) + n) = col0 ? make_float2(a0, a1) : make_float2(0.5f * (a0 + b0), 0.5f * (a1 + b1));
+                    if constexpr (KZ_LDS) *reinterpret_cast<float2*>(kzt + n) = *reinterpret_cast<const float2*>(k1 + n);
+                    if (n == 0) raw[c] = 0.5f * (a0 - b0);          // for everybody
+                }
+            }
+        }
+    });
+}
 
 // ---- half-spectrum storage geometry -------------------------------------------
 template <int N> struct Half {
@@ -476,142 +523,170 @@ template <int N> constexpr int zpass_columns() { return (N == 512 || N == 256) ?
 template <int N> constexpr bool zpass_has_width2() { return zpass_columns<N>() == 2 && N >= 1024 && N <= 2048; }
 
 // The first-stage input of one z-axis transform at element e of a spectrum column: pair 0 (uz Tz, -ux Tx), pair 1
-// (-kz Tz, kx Tx), pair 2 (kx ux S+, kz uz S+), pair 3 (S+, g3 kx uz Tc).  ONE definition with contraction off, so that every
-// z-pass variant (two or four transforms per batch, one or two columns per workgroup) feeds bit-identical values to its
-// transforms: frames are bit-identical whatever variant the launcher picks (tests/test_parity_bench_regimes.py).
+// (-kz Tz, kx Tx), pair 2 (kx ux S+, kz uz S+), pair 3 (S+, g3 kx uz Tc).  ONE place with contraction off, two siblings with the same
+// operations in the same order -- zpass_input_slot for a batch of several pairs, zpass_input<PAIR> for a single one -- and every z-pass
+// form (one, two or four transforms per batch, one or two columns per workgroup, the one-launch frame) takes its inputs from them,
+// so all of them feed bit-identical values to their transforms: frames are bit-identical whatever form the launcher picks
+// (tests/test_variants_gpu.py, tests/test_parity_bench_regimes.py).
+// zpass_input_slot: a batch interleaves SLOTS transforms, slot c = pair FIRST + c (c is a run-time index of the batch; the slot is a
+// choice between values, never a branch around the arithmetic).  choppy / full7: 1 or 0 -- the four-transform batch runs all its
+// slots in every mode and zeroes pairs 0, 1 outside the modes with a horizontal displacement, pair 2 outside the 7-field modes (a
+// product with 1.0f is exact); the other forms skip those batches and pass 1.0f.  tc: the cross derivative kx kz / |k| is odd in kx
+// and in kz separately, so on the self-mirrored Nyquist column (nb == 0) or row (e == 0) -- where one component of k(-idx) keeps its
+// sign -- its Hermitian part takes S- instead of S+ (both at once: S+ again).
+template <int FIRST, int SLOTS>
+__device__ __forceinline__ c32 zpass_input_slot(int c, float kx, float kx2, float kz, float sv, float tx, float tz, float tc,
+                                                float choppy, float full7, bool jac, float g3)
+{
+#pragma clang fp contract(off)
+    static_assert(FIRST + SLOTS <= 4 && (SLOTS == 1 || SLOTS == 4 || (SLOTS == 2 && FIRST % 2 == 0)), "one pair, {pair 0, pair 1}, {pair 2, pair 3} or all four");
+    constexpr bool ODD_PAIRS = FIRST < 2, EVEN_PAIRS = FIRST + SLOTS > 2;      // the batch holds pair 0 or 1 (odd fields) / pair 2 or 3 (even fields)
+    const int pair = SLOTS == 1 ? FIRST : FIRST + c;
+    const float d = __builtin_fmaf(kz, kz, kx2);
+    const float inv = d > 1e-10f ? rsqrtf(d) : 0.0f;              // |k| > 1e-5 (.h:135)
+    if (ODD_PAIRS && (!EVEN_PAIRS || pair < 2)) {
+        const float f = (pair ? -1.0f : inv) * choppy;             // pair 1: (-kz Tz, kx Tx); pair 0: (uz Tz, -ux Tx)
+        return make_float2(kz * f * tz, -kx * f * tx);
+    }
+    const float g = full7 * inv * sv;                              // pair 2 only exists in the 7-field modes
+    return pair == 2 ? make_float2(kx2 * g, kz * kz * g) : make_float2(sv, jac ? g3 * (kx * kz * inv * tc) : 0.0f);
+}
+// One pair, known at compile time (the forms that run a column's four transforms one after the other): the same operations in the same order.
 template <int PAIR>
-__device__ __forceinline__ c32 zpass_input(float kx, float kx2, float kz, float sv, float tx, float tz, float tc, float gate, bool jac, float g3)
+__device__ __forceinline__ c32 zpass_input(float kx, float kx2, float kz, float sv, float tx, float tz, float tc, bool jac, float g3)
 {
 #pragma clang fp contract(off)
     const float d = __builtin_fmaf(kz, kz, kx2);
     const float inv = d > 1e-10f ? rsqrtf(d) : 0.0f;              // |k| > 1e-5 (.h:135)
-    if constexpr (PAIR == 0) { const float f = inv * gate; return make_float2(kz * f * tz, -kx * f * tx); }
-    else if constexpr (PAIR == 1) { const float f = -1.0f * gate; return make_float2(kz * f * tz, -kx * f * tx); }
-    else if constexpr (PAIR == 2) { const float g = gate * inv * sv; return make_float2(kx2 * g, (kz * kz) * g); }
+    if constexpr (PAIR == 0) { const float f = inv; return make_float2(kz * f * tz, -kx * f * tx); }
+    else if constexpr (PAIR == 1) { const float f = -1.0f; return make_float2(kz * f * tz, -kx * f * tx); }
+    else if constexpr (PAIR == 2) { const float g = inv * sv; return make_float2(kx2 * g, (kz * kz) * g); }
     else return make_float2(sv, jac ? g3 * (kx * kz * inv * tc) : 0.0f);
 }
+// S+(e), Tx(e), Tz(e), Tc(e) of a column from what phase 1 left: its table sp and sm0 = S-(0).  COL0: the Nyquist column, whose table
+// is G(e) = h~(e, 0): S+- are formed on the fly.
+template <int N, bool COL0>
+__device__ __forceinline__ void zpass_fetch(const float* sp, float sm0, int e, float& sv, float& tx, float& tz, float& tc)
+{
+    if constexpr (COL0) {
+        const float g1 = sp[e], g2 = sp[(N - e) & (N - 1)];
+        sv = 0.5f * (g1 + g2);
+        tx = 0.5f * (g1 - g2);
+        tz = (e == 0) ? tx : sv;
+        tc = (e == 0) ? sv : tx;
+    } else {
+        sv = sp[e];
+        tx = sv;
+        tz = (e == 0) ? sm0 : sv;
+        tc = tz;
+    }
+}
+// Where a tile's z-pass outputs go and what they are multiplied by on the way.  Half2 intermediates: pair 0 and the height scale with
+// su, pairs 1 and 2 with sk, pair 3 (Jacobian mode) with s3, the same elements at 4 bytes each from the same base addresses.  g3: the
+// cross derivative goes INTO its transform multiplied by a power of two that brings it to the height's magnitude (in fp32 as well:
+// packed with a height a thousand times its size it would inherit the height's rounding error) and comes out of the x pass divided by it.
+template <int N, bool Z16> struct ZOut {
+    float su = 1.0f, sk = 1.0f, s3 = 1.0f, g3 = 1.0f;
+    float2* __restrict__ zt;      // pairs 0..2: group g at g * Half<N>::Z_GROUP
+    float2* __restrict__ z3;      // pair 3 = (height, cross derivative), Jacobian mode
+    float2* __restrict__ zh;      // the height's half plane, every other mode
+    __device__ __forceinline__ ZOut(const FrameArgs& a, int tile)
+    {
+        using HF = Half<N>;
+        if constexpr (Z16) { const float4 zs = a.zscale[2 * tile]; su = zs.x; sk = zs.y; s3 = a.zscale[2 * tile + 1].x; }
+        if (a.mode == 3) g3 = a.zscale[2 * tile + 1].y;
+        constexpr size_t ES = Z16 ? 4 : 8;
+        zt = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.z) + (size_t)tile * HF::Z_TILE * ES);
+        z3 = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.z3) + (size_t)tile * HF::Z_GROUP * ES);
+        zh = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.zh) + (size_t)tile * HF::ZH_TILE * ES);
+    }
+};
 
+// One column, two or four transforms per batch: {pair 0, pair 1}, {pair 2, height}, or all four at once.  Side 0 of a pair's group holds
+// p = 0..N/2, side 1 holds N-p for p > N/2 (the self-mirrored positions 0 and N/2 exist on side 0 only: the x pass knows).
+// OCEAN_MODE_JACOBIAN: the height's slot becomes pair 3 = (height, dDx/dz): the cross derivative's spectrum
+// i kz * (-i ux) h~ = kz ux h~ = kx uz h~ (.cpp:330-335; both of the reference's extra fields are this one), even like the height, rides
+// in the imaginary part the height transform leaves empty.  The result is then a full complex column (not conjugate-symmetric in p any
+// more): stored like the other pairs, as z group 3.
 template <int N, int T, class P, bool COL0, bool ZNT, bool Z16, int ZC, bool ZWT = false>
 __device__ __forceinline__ void zpass_transforms(const FrameArgs& a, c32* fbuf, const float* sp, const float* kzt,
                                                  TwiddleRegs<N, ZC, T, P>& twr, float kx, float sm0, int tid,
-                                                 int tile, int nb, int batches /* bit 0: {pair 0, pair 1}, bit 1: {pair 2, height} */)
+                                                 int tile, int nb)
 {
     using HF = Half<N>;
     const float kx2 = kx * kx;
-    [[maybe_unused]] float su = 1.0f, sk = 1.0f;              // half2 intermediates: pair 0 and the height scale with su, pairs 1 and 2 with sk
-    [[maybe_unused]] float s3 = 1.0f, g3 = 1.0f;              // pair 3 (Jacobian mode): common scale of both parts, gain of the cross derivative
-    if constexpr (Z16) { const float4 zs = a.zscale[2 * tile]; su = zs.x; sk = zs.y; s3 = a.zscale[2 * tile + 1].x; }
-    // the cross derivative goes in multiplied by a power of two g that brings it to the height's magnitude (in fp32 as
-    // well: packed with a height a thousand times its size it would inherit the height's rounding error) and comes out
-    // of the x pass divided by it
-    if (a.mode == 3) g3 = a.zscale[2 * tile + 1].y;
-    // element offsets; the half2 form packs the same elements at 4 bytes each from the same base address
-    constexpr size_t ES = Z16 ? 4 : 8;
-    float2* __restrict__ zt = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.z) + (size_t)tile * HF::Z_TILE * ES);
-    float2* __restrict__ z3 = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.z3) + (size_t)tile * HF::Z_GROUP * ES);
-    float2* __restrict__ zh = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.zh) + (size_t)tile * HF::ZH_TILE * ES);
-    // side 0 holds p = 0..N/2, side 1 holds N-p for p > N/2 (the self-mirrored positions 0 and N/2 exist on side 0
-    // only: the x pass knows)
+    const ZOut<N, Z16> o(a, tile);
     ZStore<N, T, P, ZC, Z16> zo;
     zo.init(tid, nb);
-    // S+(e) and Tx(e), Tz(e)
-    auto fetch = [&](int e, float& sv, float& tx, float& tz) {
-        if constexpr (COL0) {
-            const float g1 = sp[e], g2 = sp[(N - e) & (N - 1)];
-            sv = 0.5f * (g1 + g2);
-            tx = 0.5f * (g1 - g2);
-            tz = (e == 0) ? tx : sv;
-        } else {
-            sv = sp[e];
-            tx = sv;
-            tz = (e == 0) ? sm0 : sv;
-        }
-    };
-    if constexpr (ZC == 4) {
-        // -- one batch: slot 0 = pair 0, slot 1 = pair 1, slot 2 = pair 2, slot 3 = height (or pair 3) ----------
-        const float full7 = (a.mode == 0 || a.mode == 3) ? 1.0f : 0.0f;
-        const float choppy = a.mode != 2 ? 1.0f : 0.0f;           // HEIGHT1 keeps only slot 3
-        const bool jac = a.mode == 3;
-        auto in = [&](int e, int c, int, int) -> c32 {
-            float sv, tx, tz;
-            fetch(e, sv, tx, tz);
-            const float kz = kzt[e];
-            const float d = __builtin_fmaf(kz, kz, kx2);
-            const float inv = d > 1e-10f ? rsqrtf(d) : 0.0f;      // |k| > 1e-5 (.h:135)
-            if (c < 2) {
-                const float f = (c ? -1.0f : inv) * choppy;        // pair 1: (-kz Tz, kx Tx); pair 0: (uz Tz, -ux Tx)
-                return make_float2(kz * f * tz, -kx * f * tx);
-            }
-            const float g = full7 * inv * sv;
-            const float tc = COL0 ? (e == 0 ? sv : tx) : tz;       // cross derivative: see the two-batch form below
-            return c == 2 ? make_float2(kx2 * g, kz * kz * g) : make_float2(sv, jac ? g3 * (kx * kz * inv * tc) : 0.0f);
-        };
-        auto out = [&](int p, int c, c32 v, int u, int i) {
-            const unsigned pos = zo.pos(nb, p, u, i);
-            if (c == 3) {
-                if (jac) store_z<ZNT, Z16, ZWT>(z3, pos, v, s3);
-                else if (zo.keeps(p, i)) store_z<ZNT, Z16, ZWT>(zh, zo.hpos(nb, p, u, i), v, su);
-                return;
-            }
-            if (a.mode == 2) return;
-            store_z<ZNT, Z16, ZWT>(zt, (unsigned)c * (unsigned)HF::Z_GROUP + pos, v, c == 0 ? su : sk);
-        };
-        batch_fft<N, 4, T, P>(fbuf, twr, tid, in, out);
-        return;
-    } else {
-    // -- batch A: slot 0 = pair 0 (Dx, Dz), slot 1 = pair 1 (sx, sz) ------------
-    if (a.mode != 2 && (batches & 1)) {
-        auto in = [&](int e, int c, int, int) -> c32 {
-#pragma clang fp contract(off)
-            float sv, tx, tz;
-            fetch(e, sv, tx, tz);
-            // (same operations, same order as zpass_input<0/1>, no contraction: bit-identical to the two-column variant)
-            const float kz = kzt[e];
-            const float d = __builtin_fmaf(kz, kz, kx2);
-            const float inv = d > 1e-10f ? rsqrtf(d) : 0.0f;      // |k| > 1e-5 (.h:135)
-            const float f = c ? -1.0f : inv;                       // pair 1: (-kz Tz, kx Tx); pair 0: (uz Tz, -ux Tx)
-            return make_float2(kz * f * tz, -kx * f * tx);
-        };
-        auto out = [&](int p, int c, c32 v, int u, int i) {
-            store_z<ZNT, Z16, ZWT>(zt, (unsigned)c * (unsigned)HF::Z_GROUP + zo.pos(nb, p, u, i), v, c ? sk : su);
-        };
-        batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
-    }
-    // -- batch B: slot 0 = pair 2 (dDx/dx, dDz/dz), slot 1 = height ----------------
-    // OCEAN_MODE_JACOBIAN: slot 1 becomes pair 3 = (height, dDx/dz): the cross derivative's spectrum
-    // i kz * (-i ux) h~ = kz ux h~ = kx uz h~ (.cpp:330-335; both of the reference's extra fields are this one), even
-    // like the height, rides in the imaginary part the height transform leaves empty.  The result is then a full
-    // complex column (not conjugate-symmetric in p any more): stored like the other pairs, as z group 3.
     const float full7 = (a.mode == 0 || a.mode == 3) ? 1.0f : 0.0f;
     const bool jac = a.mode == 3;
-    if (batches & 2) {
+    // the batch whose slot c is pair FIRST + c
+    auto batch = [&](auto first, float choppy) {
+        constexpr int FIRST = decltype(first)::value;
         auto in = [&](int e, int c, int, int) -> c32 {
-#pragma clang fp contract(off)
-            float sv, tx, tz;
-            fetch(e, sv, tx, tz);
-            const float kz = kzt[e];
-            // cross derivative: kx kz / |k| is odd in kx and in kz separately, so on the self-mirrored Nyquist column
-            // (nb == 0) or row (e == 0) -- where one component of k(-idx) keeps its sign -- its Hermitian part takes
-            // S- instead of S+ (both at once: S+ again)
-            const float tc = COL0 ? (e == 0 ? sv : tx) : tz;
-            // (same operations, same order as zpass_input<2/3>, no contraction)
-            const float kz2 = kz * kz;
-            const float d = __builtin_fmaf(kz, kz, kx2);
-            const float inv = d > 1e-10f ? rsqrtf(d) : 0.0f;
-            const float g = full7 * inv * sv;                      // pair 2 only exists in the 7-field modes
-            return make_float2(c ? sv : kx2 * g, c ? (jac ? g3 * (kx * kz * inv * tc) : 0.0f) : kz2 * g);
+            float sv, tx, tz, tc;
+            zpass_fetch<N, COL0>(sp, sm0, e, sv, tx, tz, tc);
+            return zpass_input_slot<FIRST, ZC>(c, kx, kx2, kzt[e], sv, tx, tz, tc, choppy, full7, jac, o.g3);
         };
         auto out = [&](int p, int c, c32 v, int u, int i) {
-            if (c) {
-                if (jac) store_z<ZNT, Z16, ZWT>(z3, zo.pos(nb, p, u, i), v, s3);
-                else if (zo.keeps(p, i)) store_z<ZNT, Z16, ZWT>(zh, zo.hpos(nb, p, u, i), v, su);     // real input: other half is the conjugate
+            const int pair = FIRST + c;
+            const unsigned pos = zo.pos(nb, p, u, i);
+            if (FIRST + ZC == 4 && pair == 3) {
+                if (jac) store_z<ZNT, Z16, ZWT>(o.z3, pos, v, o.s3);
+                else if (zo.keeps(p, i)) store_z<ZNT, Z16, ZWT>(o.zh, zo.hpos(nb, p, u, i), v, o.su);     // real input: other half is the conjugate
                 return;
             }
-            store_z<ZNT, Z16, ZWT>(zt, 2u * (unsigned)HF::Z_GROUP + zo.pos(nb, p, u, i), v, sk);
+            if (ZC == 4 && a.mode == 2) return;                    // HEIGHT1 keeps only slot 3
+            store_z<ZNT, Z16, ZWT>(o.zt, (unsigned)pair * (unsigned)HF::Z_GROUP + pos, v, pair == 0 ? o.su : o.sk);
         };
-        batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
+        batch_fft<N, ZC, T, P>(fbuf, twr, tid, in, out);
+    };
+    if constexpr (ZC == 4) {
+        batch(std::integral_constant<int, 0>{}, a.mode != 2 ? 1.0f : 0.0f);
+    } else {
+        if (a.mode != 2) batch(std::integral_constant<int, 0>{}, 1.0f);
+        batch(std::integral_constant<int, 2>{}, 1.0f);
     }
+}
+
+// Four single-pair batches one after the other -- pair 0, pair 1, pair 2, then the height (or pair 3 of the Jacobian mode) -- ZC transforms of
+// the same pair side by side: the two neighbouring columns of zpass_two_columns (k_zpass_c1 keeps its own sequence: zpass_single_transforms).
+// fetch(e, c, kx, kx2, sv, tx, tz, tc): the inputs of slot c's column at element e; col(c): that column, nb0 being the first.
+// kz of a thread's first-stage inputs -- elements j + i * (N / R0), i = 0 .. R0-1, in every one of the four batches, whichever slot its
+// transform is -- lives in registers (kzr[i], fetched once per workgroup from the k table) instead of an LDS table: N floats less LDS
+// (4096: three workgroups per CU instead of two; two columns at 2048: 51 instead of 59 KB, three instead of two) and a quarter of the
+// first stages' LDS reads.
+template <int N, int ZC, int T, class P, bool ZNT, bool Z16, bool ZWT, class F, class C>
+__device__ __forceinline__ void zpass_pair_batches(const FrameArgs& a, c32* fbuf, TwiddleRegs<N, ZC, T, P>& twr, const float (&kzr)[P::r[0]],
+                                                   int tid, int tile, int nb0, F&& fetch, C&& col)
+{
+    using HF = Half<N>;
+    static_assert(FirstStage<N, ZC, T, P>::IT == 1, "one first-stage butterfly per thread");
+    const ZOut<N, Z16> o(a, tile);
+    const bool jac = a.mode == 3;
+    ZStore<N, T, P, ZC, Z16> zo;
+    zo.init(tid, nb0, ZC == 2);
+    auto batch = [&](auto pair) {
+        constexpr int PAIR = decltype(pair)::value;
+        auto in = [&](int e, int c, int, int i) -> c32 {
+            float kx, kx2, sv, tx, tz, tc;
+            fetch(e, c, kx, kx2, sv, tx, tz, tc);
+            if (PAIR == 3 && !jac) return make_float2(sv, 0.0f);
+            return zpass_input<PAIR>(kx, kx2, kzr[i], sv, tx, tz, tc, PAIR == 3, o.g3);
+        };
+        auto out = [&](int p, int c, c32 v, int u, int i) {
+            if constexpr (PAIR < 3) store_z<ZNT, Z16, ZWT>(o.zt, (unsigned)PAIR * (unsigned)HF::Z_GROUP + zo.pos(col(c), p, u, i), v, PAIR == 0 ? o.su : o.sk);
+            else if (jac) store_z<ZNT, Z16, ZWT>(o.z3, zo.pos(col(c), p, u, i), v, o.s3);
+            else if (zo.keeps(p, i)) store_z<ZNT, Z16, ZWT>(o.zh, zo.hpos(col(c), p, u, i), v, o.su);     // real input: other half is the conjugate
+        };
+        batch_fft<N, ZC, T, P>(fbuf, twr, tid, in, out);
+    };
+    if (a.mode != 2) {
+        batch(std::integral_constant<int, 0>{});
+        batch(std::integral_constant<int, 1>{});
     }
+    if (a.mode == 0 || a.mode == 3) batch(std::integral_constant<int, 2>{});     // only the 7-field modes read pair 2
+    batch(std::integral_constant<int, 3>{});
 }
 
 // Two neighbouring spectrum columns nb0, nb0 + 1 (neither the Nyquist column 0 nor beyond N/2) in one workgroup: four batches
@@ -621,110 +696,28 @@ template <int N, int T, class P, bool ZNT, bool Z16, bool FAST>
 __device__ __forceinline__ void zpass_two_columns(const FrameArgs& a, unsigned char* smem, TwiddleRegs<N, 2, T, P>& twr,
                                                   int tid, int tile, int nb0)
 {
-    using HF = Half<N>;
     c32* fbuf = reinterpret_cast<c32*>(smem);
     float* sp0 = reinterpret_cast<float*>(fbuf + fft_lds_elems<N, 2>());   // S+ of column nb0, of column nb0 + 1
     float* sp1 = sp0 + N;
     float* raw = reinterpret_cast<float*>(fbuf);                           // [0], [1]: S-(0) of the two columns, until the first exchange
-    const float t = a.t + (a.toff ? a.toff[tile] : 0.0f);
+    zpass_phase1<N, T, 2, false, ZNT, FAST>(a, tile, nb0, tid, sp0, nullptr, raw);
     const float* __restrict__ k1 = a.k1d + (size_t)tile * N;
-    const float h16s = a.h0h ? a.h0_inv_scale[tile] : 1.0f;
-    const float base = a.omega_q ? a.base_freq[tile] : 0.0f;
-    spectrum_form<FAST>(a, [&](auto h16, auto w16) {   // phase 1: columns nb0 and nb0 + 1, each with its mirror (zpass_load_pair)
-        constexpr bool H16 = decltype(h16)::value, W16 = decltype(w16)::value;
-        constexpr int ITEMS = N;                      // 2 columns * N/2 element pairs
-        constexpr int P1 = ITEMS / T;
-        constexpr int PB = P1 > 2 ? 2 : P1;           // items in flight per thread (ten registers each; four spill under 2048's cap)
-        static_assert(ITEMS % T == 0 && P1 % PB == 0, "phase-1 batches");
-#pragma unroll 1
-        for (int ub = 0; ub < P1; ub += PB) {
-            float4 ha[PB];
-            float2 hb0[PB], hb1[PB], wv[PB];
-#pragma unroll
-            for (int u = 0; u < PB; ++u) {
-                const int it = tid + (ub + u) * T;
-                zpass_load_pair<N, H16, W16, ZNT>(a, tile, nb0 + it / (N / 2), 2 * (it % (N / 2)), h16s, base, ha[u], hb0[u], hb1[u], wv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < PB; ++u) {
-                const int it = tid + (ub + u) * T;
-                const int c = it / (N / 2), n = 2 * (it % (N / 2));
-                float a0, b0, a1, b1;
-                animate_with_mirror(make_float2(ha[u].x, ha[u].y), hb0[u], wv[u].x, t, a0, b0);
-                animate_with_mirror(make_float2(ha[u].z, ha[u].w), hb1[u], wv[u].y, t, a1, b1);
-                *reinterpret_cast<float2*>((c ? sp1 : sp0) + n) = make_float2(0.5f * (a0 + b0), 0.5f * (a1 + b1));
-                if (n == 0) raw[c] = 0.5f * (a0 - b0);
-            }
-        }
-    });
-    // kz of this thread's first-stage inputs: elements j + i * (N / R0) in every one of the four batches, whichever column the thread's
-    // transform belongs to -- in registers (from the k table, once per workgroup) instead of an LDS table: N floats less LDS (2048: 51
-    // instead of 59 KB, three workgroups per CU instead of two) and a third of the first stages' LDS reads
-    static_assert(FirstStage<N, 2, T, P>::IT == 1, "one first-stage butterfly per thread");
     float kzr[P::r[0]];
 #pragma unroll
     for (int i = 0; i < P::r[0]; ++i) kzr[i] = k1[tid / 2 + i * (N / P::r[0])];
     __syncthreads();
     const float sm00 = raw[0], sm01 = raw[1];      // S-(0) of the two columns
-
-    [[maybe_unused]] float su = 1.0f, sk = 1.0f, s3 = 1.0f;
-    float g3 = 1.0f;
-    if constexpr (Z16) { const float4 zs = a.zscale[2 * tile]; su = zs.x; sk = zs.y; s3 = a.zscale[2 * tile + 1].x; }
-    if (a.mode == 3) g3 = a.zscale[2 * tile + 1].y;
-    constexpr size_t ES = Z16 ? 4 : 8;
-    float2* __restrict__ zt = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.z) + (size_t)tile * HF::Z_TILE * ES);
-    float2* __restrict__ z3 = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.z3) + (size_t)tile * HF::Z_GROUP * ES);
-    float2* __restrict__ zh = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.zh) + (size_t)tile * HF::ZH_TILE * ES);
     const float kx0 = k1[nb0], kx1 = k1[nb0 + 1];
-    const bool jac = a.mode == 3;
-    ZStore<N, T, P, 2, Z16> zo;
-    zo.init(tid, nb0, true);
-    // S+(e), Tz(e) (Tx = S+ off the Nyquist column), kx of column c
     const float kx20 = kx0 * kx0, kx21 = kx1 * kx1;
-    auto fetch = [&](int e, int c, float& sv, float& tz, float& kx, float& kx2) {
+    // off the Nyquist column Tx = S+ and Tc = Tz
+    auto fetch = [&](int e, int c, float& kx, float& kx2, float& sv, float& tx, float& tz, float& tc) {
         sv = c ? sp1[e] : sp0[e];
         tz = (e == 0) ? (c ? sm01 : sm00) : sv;
         kx = c ? kx1 : kx0;
         kx2 = c ? kx21 : kx20;
+        tx = sv; tc = tz;
     };
-    if (a.mode != 2) {
-        if (a.zmask & 1) {   // pair 0: (uz Tz, -ux Tx)
-            auto in = [&](int e, int c, int, int i) -> c32 {
-                float sv, tz, kx, kx2; fetch(e, c, sv, tz, kx, kx2);
-                return zpass_input<0>(kx, kx2, kzr[i], sv, sv, tz, tz, 1.0f, false, 1.0f);
-            };
-            auto out = [&](int p, int c, c32 v, int u, int i) { store_z<ZNT, Z16>(zt, zo.pos(nb0 + c, p, u, i), v, su); };
-            batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
-        }
-        if (a.zmask & 2) {   // pair 1: (-kz Tz, kx Tx)
-            auto in = [&](int e, int c, int, int i) -> c32 {
-                float sv, tz, kx, kx2; fetch(e, c, sv, tz, kx, kx2);
-                return zpass_input<1>(kx, kx2, kzr[i], sv, sv, tz, tz, 1.0f, false, 1.0f);
-            };
-            auto out = [&](int p, int c, c32 v, int u, int i) { store_z<ZNT, Z16>(zt, (unsigned)HF::Z_GROUP + zo.pos(nb0 + c, p, u, i), v, sk); };
-            batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
-        }
-    }
-    if ((a.mode == 0 || a.mode == 3) && (a.zmask & 4)) {   // pair 2: (kx ux S+, kz uz S+) -- only the 7-field modes read it
-        auto in = [&](int e, int c, int, int i) -> c32 {
-            float sv, tz, kx, kx2; fetch(e, c, sv, tz, kx, kx2);
-            return zpass_input<2>(kx, kx2, kzr[i], sv, sv, tz, tz, 1.0f, false, 1.0f);
-        };
-        auto out = [&](int p, int c, c32 v, int u, int i) { store_z<ZNT, Z16>(zt, 2u * (unsigned)HF::Z_GROUP + zo.pos(nb0 + c, p, u, i), v, sk); };
-        batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
-    }
-    if (a.zmask & 8) {   // height (or pair 3 = (height, cross derivative) of the Jacobian mode)
-        auto in = [&](int e, int c, int, int i) -> c32 {
-            float sv, tz, kx, kx2; fetch(e, c, sv, tz, kx, kx2);
-            if (!jac) return make_float2(sv, 0.0f);
-            return zpass_input<3>(kx, kx2, kzr[i], sv, sv, tz, tz, 1.0f, true, g3);
-        };
-        auto out = [&](int p, int c, c32 v, int u, int i) {
-            if (jac) store_z<ZNT, Z16>(z3, zo.pos(nb0 + c, p, u, i), v, s3);
-            else if (zo.keeps(p, i)) store_z<ZNT, Z16>(zh, zo.hpos(nb0 + c, p, u, i), v, su);     // real input: other half is the conjugate
-        };
-        batch_fft<N, 2, T, P>(fbuf, twr, tid, in, out);
-    }
+    zpass_pair_batches<N, 2, T, P, ZNT, Z16, false>(a, fbuf, twr, kzr, tid, tile, nb0, fetch, [&](int c) { return nb0 + c; });
 }
 
 // ============================================================================
@@ -765,48 +758,11 @@ __device__ __forceinline__ void zpass_body(const FrameArgs& a, unsigned char* sm
     static_assert(ZW == 1 || zpass_has_width2<N>(), "two columns per workgroup: two-batch sizes from 1024 up");
     TwiddleRegs<N, ZC, T, P> twr;
     twr.load(a.tw, tid);
-    auto one_column = [&](const int nb, const int batches) {
-    const float t = a.t + (a.toff ? a.toff[tile] : 0.0f);
+    auto one_column = [&](const int nb) {
+    zpass_phase1<N, T, 1, true, ZNT, FAST>(a, tile, nb, tid, sp, kzt, raw);
     const float* __restrict__ k1 = a.k1d + (size_t)tile * N;               // [N], cache-resident table
     const bool col0 = (nb == 0);
-    const float h16s = a.h0h ? a.h0_inv_scale[tile] : 1.0f;
-    const float base = a.omega_q ? a.base_freq[tile] : 0.0f;
-
-    // -- phase 1: animate column nb with its mirror nbb (zpass_load_pair); all loads issued before the first sincos.
-    // S- is needed along the whole column only for the Nyquist column nb == 0 (Tx = S-); every other column needs just
-    // S-(0) (Tz at e == 0) and keeps the kz table in LDS instead.  The Nyquist column pairs with itself (nbb == 0): S+ is
-    // even and S- odd along e, so ONE array G(e) = h~(e, 0) carries both; every other column stores S+ directly.
-    spectrum_form<FAST>(a, [&](auto h16, auto w16) {
-        constexpr bool H16 = decltype(h16)::value, W16 = decltype(w16)::value;
-        constexpr int PAIRS = N / 2;
-        constexpr int P1 = (PAIRS + T - 1) / T;
-        constexpr int PB = P1 > 4 ? 4 : P1;          // items in flight per thread
-        static_assert(P1 % PB == 0, "phase-1 batches");
-#pragma unroll 1
-        for (int ub = 0; ub < P1; ub += PB) {
-            float4 ha[PB];
-            float2 hb0[PB], hb1[PB], wv[PB];
-#pragma unroll
-            for (int u = 0; u < PB; ++u) {
-                const int it = tid + (ub + u) * T;
-                if (PAIRS % T == 0 || it < PAIRS) zpass_load_pair<N, H16, W16, ZNT>(a, tile, nb, 2 * it, h16s, base, ha[u], hb0[u], hb1[u], wv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < PB; ++u) {
-                const int it = tid + (ub + u) * T;
-                if (PAIRS % T == 0 || it < PAIRS) {
-                    const int n = 2 * it;
-                    float a0, b0, a1, b1;
-                    animate_with_mirror(make_float2(ha[u].x, ha[u].y), hb0[u], wv[u].x, t, a0, b0);
-                    animate_with_mirror(make_float2(ha[u].z, ha[u].w), hb1[u], wv[u].y, t, a1, b1);
-                    *reinterpret_cast<float2*>(sp + n) = col0 ? make_float2(a0, a1) : make_float2(0.5f * (a0 + b0), 0.5f * (a1 + b1));
-                    *reinterpret_cast<float2*>(kzt + n) = *reinterpret_cast<const float2*>(k1 + n);
-                    if (n == 0) raw[0] = 0.5f * (a0 - b0);          // S-(0), for everybody (the FFT image is not in use yet)
-                }
-            }
-        }
-    });
-    if (bx == 0 && tid == 0 && (a.zmask & 8)) {   // (the launch that transforms the height: ahead of the HEIGHT workgroups' atomics)
+    if (bx == 0 && tid == 0) {   // (ahead of the HEIGHT workgroups' atomics)
         // min starts at FLT_MAX, max at FLT_MIN (> 0): WSTessendorf.cpp:289-290
         if constexpr (ONE) {        // the atomics of this very launch's HEIGHT workgroups follow (behind zdone): the resets must not sit in this XCD's L2
             __hip_atomic_store(a.minmax + 2 * tile + 0, float_key(3.402823466e+38f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -821,8 +777,8 @@ __device__ __forceinline__ void zpass_body(const FrameArgs& a, unsigned char* sm
     __syncthreads();
     const float sm0 = raw[0];
 
-    if (col0) zpass_transforms<N, T, P, true, ZNT, Z16, ZC, ONE>(a, fbuf, sp, kzt, twr, k1[nb], sm0, tid, tile, nb, batches);
-    else zpass_transforms<N, T, P, false, ZNT, Z16, ZC, ONE>(a, fbuf, sp, kzt, twr, k1[nb], sm0, tid, tile, nb, batches);
+    if (col0) zpass_transforms<N, T, P, true, ZNT, Z16, ZC, ONE>(a, fbuf, sp, kzt, twr, k1[nb], sm0, tid, tile, nb);
+    else zpass_transforms<N, T, P, false, ZNT, Z16, ZC, ONE>(a, fbuf, sp, kzt, twr, k1[nb], sm0, tid, tile, nb);
     };
 
     if constexpr (ZW == 2) {
@@ -834,12 +790,12 @@ __device__ __forceinline__ void zpass_body(const FrameArgs& a, unsigned char* sm
             zpass_two_columns<N, T, P, ZNT, Z16, FAST>(a, smem, twr, tid, tile, 2 * blk);
             return;
         }
-        if (blk == LAST) { one_column(N / 2, 3); return; }
-        one_column(0, 3);
+        if (blk == LAST) { one_column(N / 2); return; }
+        one_column(0);
         __syncthreads();            // the slowest wave is done with the FFT image before the next column's h~ overwrites it
-        one_column(1, 3);
+        one_column(1);
     } else {
-        one_column(xcd_swizzle(bx, gx), 3);     // neighbouring columns write neighbouring pieces of the same lines: same XCD, same L2
+        one_column(xcd_swizzle(bx, gx));     // neighbouring columns write neighbouring pieces of the same lines: same XCD, same L2
     }
 }
 
@@ -909,6 +865,10 @@ struct ClockProbe {
 // workgroups per CU, the same number of waves, and each one's load burst and store tail travel under the other's transforms.  Same radix
 // plan, same inputs (zpass_input), same twiddles: bit-identical to the other forms (tests/test_variants_gpu.py).
 // ============================================================================
+// k_zpass_c1 is kept as it was -- its own phase 1, fetch, output set-up and batch sequence, the always-true tests of FrameArgs::zmask around
+// the batches -- and compiles to the parent's instructions: routed through zpass_phase1 / ZOut / zpass_pair_batches its instantiations with
+// every form of the spectrum measured 1.5-2 % slower at 2048^2 and the half2 ones at 1024^2 spilled 16 bytes
+// (profiles/r07_zpass_one_definition.txt).  Its inputs come from zpass_input like everybody's.
 template <int N, int T, class P, bool COL0, bool ZNT, bool Z16, bool ZWT = false>
 __device__ __forceinline__ void zpass_single_transforms(const FrameArgs& a, c32* fbuf, const float* sp, const float (&kzr)[P::r[0]],
                                                         TwiddleRegs<N, 1, T, P>& twr, float kx, float sm0, int tid, int tile, int nb)
@@ -945,12 +905,12 @@ __device__ __forceinline__ void zpass_single_transforms(const FrameArgs& a, c32*
             tc = tz;
         }
     };
-    // (a.zmask: which of the four this launch runs -- all of them: only round 5's split frame order ran halves; wave-uniform)
+    // (a.zmask: always 15; the tests keep the four batches apart for the scheduler -- see FrameArgs::zmask)
     if (a.mode != 2) {
         if (a.zmask & 1) {   // pair 0: (uz Tz, -ux Tx)
             auto in = [&](int e, int, int, int i) -> c32 {
                 float sv, tx, tz, tc; fetch(e, sv, tx, tz, tc);
-                return zpass_input<0>(kx, kx2, kzr[i], sv, tx, tz, tc, 1.0f, false, 1.0f);
+                return zpass_input<0>(kx, kx2, kzr[i], sv, tx, tz, tc, false, 1.0f);
             };
             auto out = [&](int p, int, c32 v, int u, int i) { store_z<ZNT, Z16, ZWT>(zt, zo.pos(nb, p, u, i), v, su); };
             batch_fft<N, 1, T, P>(fbuf, twr, tid, in, out);
@@ -958,7 +918,7 @@ __device__ __forceinline__ void zpass_single_transforms(const FrameArgs& a, c32*
         if (a.zmask & 2) {   // pair 1: (-kz Tz, kx Tx)
             auto in = [&](int e, int, int, int i) -> c32 {
                 float sv, tx, tz, tc; fetch(e, sv, tx, tz, tc);
-                return zpass_input<1>(kx, kx2, kzr[i], sv, tx, tz, tc, 1.0f, false, 1.0f);
+                return zpass_input<1>(kx, kx2, kzr[i], sv, tx, tz, tc, false, 1.0f);
             };
             auto out = [&](int p, int, c32 v, int u, int i) { store_z<ZNT, Z16, ZWT>(zt, (unsigned)HF::Z_GROUP + zo.pos(nb, p, u, i), v, sk); };
             batch_fft<N, 1, T, P>(fbuf, twr, tid, in, out);
@@ -967,7 +927,7 @@ __device__ __forceinline__ void zpass_single_transforms(const FrameArgs& a, c32*
     if ((a.mode == 0 || a.mode == 3) && (a.zmask & 4)) {   // pair 2: (kx ux S+, kz uz S+) -- only the 7-field modes read it
         auto in = [&](int e, int, int, int i) -> c32 {
             float sv, tx, tz, tc; fetch(e, sv, tx, tz, tc);
-            return zpass_input<2>(kx, kx2, kzr[i], sv, tx, tz, tc, 1.0f, false, 1.0f);
+            return zpass_input<2>(kx, kx2, kzr[i], sv, tx, tz, tc, false, 1.0f);
         };
         auto out = [&](int p, int, c32 v, int u, int i) { store_z<ZNT, Z16, ZWT>(zt, 2u * (unsigned)HF::Z_GROUP + zo.pos(nb, p, u, i), v, sk); };
         batch_fft<N, 1, T, P>(fbuf, twr, tid, in, out);
@@ -976,7 +936,7 @@ __device__ __forceinline__ void zpass_single_transforms(const FrameArgs& a, c32*
         auto in = [&](int e, int, int, int i) -> c32 {
             float sv, tx, tz, tc; fetch(e, sv, tx, tz, tc);
             if (!jac) return make_float2(sv, 0.0f);
-            return zpass_input<3>(kx, kx2, kzr[i], sv, tx, tz, tc, 1.0f, true, g3);
+            return zpass_input<3>(kx, kx2, kzr[i], sv, tx, tz, tc, true, g3);
         };
         auto out = [&](int p, int, c32 v, int u, int i) {
             if (jac) store_z<ZNT, Z16, ZWT>(z3, zo.pos(nb, p, u, i), v, s3);
@@ -1236,12 +1196,12 @@ __device__ __forceinline__ void frame_records(const FrameArgs& a, unsigned* lds_
     }
 }
 
-// The body of k_xpass_b as a device function (k_frame runs it for the workgroups behind its z-pass ones).  bx_in: the workgroup's index among
+// The body of k_xpass_b as a device function (k_frame runs it for the workgroups behind its z-pass ones).  bx: the workgroup's index among
 // the launch's x-axis workgroups; ONE: part of a one-launch frame -- all three roles (HEIGHT, NORMAL, DISP), every workgroup first waits until
 // the tile's z-pass workgroups of the same launch have counted themselves in (FrameArgs::zdone; they are dispatched first and wait for nobody),
 // and the records' workgroup count leaves the z-pass workgroups out (rec_total / rec_id).
 template <int N, int C, int T, class P, bool NTS, bool Z16, bool JAC, bool ONE = false>
-__device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* smem, const int bx_in, const unsigned rec_total = 0, const unsigned rec_id = 0)
+__device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* smem, const int bx, const unsigned rec_total = 0, const unsigned rec_id = 0)
 {
     using HF = Half<N>;
     c32* fbuf = reinterpret_cast<c32*>(smem);
@@ -1253,8 +1213,6 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     constexpr int NB = (HF::NU + C - 1) / C;              // normal workgroups
     constexpr int HB = JAC ? NB : xpass_height_groups<N, C>();      // height workgroups
     static_assert(HF::NUP % (2 * C) == 0, "height row blocks");
-    // a launch holds the HEIGHT workgroups, the NORMAL workgroups or (usually) both: a.xb_roles; bx = the index in the full grid
-    const int bx = bx_in + (a.xb_roles == 2 ? HB : 0);
     if constexpr (ONE) wait_counter_reached(a.zdone + tile, a.zdone_target, tid, a.poll_sleep, a.fault);      // the intermediates of THIS frame are all written (write-through)
 
     // (the roles are lambdas: every workgroup of a launch, whatever its role, ends in frame_records)
@@ -1302,10 +1260,10 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     }
     };
     // ---- HEIGHT workgroup: C transforms of two real rows each, raw signed heights out, global min / max by atomics.  In a merged x pass
-    // (xb_roles bit 2) the DISP workgroups of the same launch read those rows and the final min / max: the rows are stored write-through
+    // (xb_disp) the DISP workgroups of the same launch read those rows and the final min / max: the rows are stored write-through
     // and the workgroup announces itself on a.hdone behind them (store_wt / wait_counter above).
     auto height_role = [&]() {
-        const bool merged = (a.xb_roles & 4) != 0;
+        const bool merged = a.xb_disp != 0;
         constexpr int NW = (T + 63) / 64;
         float* red = reinterpret_cast<float*>(fbuf + fft_lds_elems<N, C>());
         const int u0 = xcd_swizzle(bx, HB) * 2 * C;
@@ -1496,7 +1454,7 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         batch_fft<N, C, T, P>(fbuf, twr, tid, in, out);
     }
     };
-    // ---- DISP workgroup of a merged x pass (xb_roles bit 2; never in the Jacobian mode): pair 0 -> displacement-map rows u0 .. u0+C-1, like
+    // ---- DISP workgroup of a merged x pass (xb_disp; never in the Jacobian mode): pair 0 -> displacement-map rows u0 .. u0+C-1, like
     // k_xpass_disp, in the SAME launch as the HEIGHT workgroups whose rows and min / max it needs.  It transforms at once and holds the
     // results; only then does it wait for the tile's HEIGHT workgroups (dispatched before it: lower block indices, and they wait for
     // nobody, so the wait cannot deadlock whatever is resident), reads its raw heights and the final keys write-through, and stores.
@@ -1543,12 +1501,12 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
             });
         }
     };
-    const bool merged_launch = (a.xb_roles & 4) != 0;
+    const bool merged_launch = a.xb_disp != 0;
     if (bx < HB) { if constexpr (JAC) pair3_role(); else height_role(); }
     else if (!JAC && merged_launch && bx >= HB + NB) disp_role();
     else normal_role();
-    // the launch's records: the early form needs the final height keys -- the first NORMAL workgroup of a launch behind the HEIGHT
-    // workgroups' launch (xb_roles 2), the first DISP workgroup of a merged launch (it has waited for them)
+    // the launch's records: the early form needs the final height keys -- the first DISP workgroup of a merged launch (it has waited for them;
+    // a launch without DISP workgroups is never a frame's last and is asked for no records)
     frame_records<T>(a, reinterpret_cast<unsigned*>(smem), tid, merged_launch ? bx == HB + NB : bx == HB, rec_total, rec_id);
 }
 

@@ -132,8 +132,9 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
     // Frame order: z pass (four transforms per column) -> k_xpass_b (HEIGHT + NORMAL workgroups) -> k_xpass_disp.  (Round 5 also ran a SPLIT
     // order -- z pass {height, pair 0} -> HEIGHT workgroups -> k_xpass_disp -> z pass {pair 1, pair 2} -> NORMAL workgroups: bit-identical, slower
     // at every size -- the x passes sit on the map write stream, not on their reads, and the second animation of the spectrum is paid in full;
-    // profiles/r05_4096_experiments.txt.  The per-launch fields it needed -- zmask, xb_roles, rec_mode -- are still part of every launch.)
-    // Merged x pass (round 5): HEIGHT, NORMAL and DISP workgroups in ONE launch of k_xpass_b (xb_roles = 7) instead of k_xpass_b + k_xpass_disp.
+    // profiles/r05_4096_experiments.txt.  Of the per-launch fields it needed, rec_mode is still part of every launch: which launch is the frame's last
+    // depends on the form; the mask of x-axis roles went with it, the mask of transforms is always 15 and only k_zpass_c1 still tests it: FrameArgs::zmask.)
+    // Merged x pass (round 5): HEIGHT, NORMAL and DISP workgroups in ONE launch of k_xpass_b (xb_disp) instead of k_xpass_b + k_xpass_disp.
     // The DISP workgroups transform pair 0 at once and wait for the tile's HEIGHT workgroups only before their stores (raw heights handed over
     // write-through, ocean_kernels.h: store_wt / wait_counter): a small single tile is three short DEPENDENT latency chains
     // (profiles/r02_small_tile_experiments.txt item 0), and this runs the third one beside the second.  Where every workgroup of the launch
@@ -256,7 +257,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
         if (merged) describe(2, gb.x, G::T_C, C, lds_b, flags_b | (p.nt_disp ? OCEAN_LAUNCH_NT_MAPS : 0u));
         hipEvent_t* mb = next_marks(1);
         FrameArgs ba = a;
-        ba.xb_roles = merged ? 7 : 3; ba.rec_mode = merged ? rec_last : 0;
+        ba.xb_disp = merged ? 1 : 0; ba.rec_mode = merged ? rec_last : 0;
         ba.poll_sleep = poll_sleep;
         ba.start_ramp = ramp_b;             // over its normal-map workgroups (the height workgroups start at once)
         if (p.nt_normal) OCEAN_XPASS(k_xpass_b, gb, lds_b, mb, true, ba);
@@ -281,7 +282,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
                 c->attr_one_n = (uint32_t)N;
             }
             FrameArgs fa = a;
-            fa.xb_roles = 7; fa.rec_mode = rec_last; fa.start_ramp = 0;
+            fa.xb_disp = 1; fa.rec_mode = rec_last; fa.start_ramp = 0;
             fa.zdone_target = (++c->zgen[fl.set]) * (unsigned)(N / 2 + 1);
             fa.poll_sleep = poll_sleep;
             const dim3 grid((N / 2 + 1) + hb_b + 2 * nb, tiles), block(G::T_C);
