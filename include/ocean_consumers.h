@@ -53,6 +53,24 @@ int ocean_build_mips(ocean_t* ctx, uint32_t tile);
 int ocean_read_mips(ocean_t* ctx, float* disp_mips, float* nrm_mips);
 int ocean_device_mips(ocean_t* ctx, void** d_disp_mips, void** d_nrm_mips, uint32_t* levels);
 
+/* Mip chains of a tile range: what the LOD sampler below reads.  ocean_build_mips_tiles builds the chains of both maps of the tiles
+ * first_tile .. first_tile+count-1 (count 1 .. tiles - first_tile) from the most recently enqueued frame, stream-ordered behind it like
+ * every other consumer (any pipeline depth, caller-bound or imported output), in at most two kernel launches whatever the count.  Two
+ * buffers owned by the context, one per map, hold [count][ocean_mip_texels(N)] float4: tile i of the range keeps the packed layout of
+ * ocean_build_mips, so level l of tile i starts at texel i * ocean_mip_texels(N) + sum_{k=1}^{l-1} (N >> k)^2.  Every texel of every
+ * level carries exactly the bits of ocean_build_mips' chain: (t00*0.5f + t10*0.5f)*0.5f + (t01*0.5f + t11*0.5f)*0.5f of the level above,
+ * no contraction.  The buffers grow on demand (a growth that fails leaves no set), survive a new tile size and go with ocean_destroy.  The
+ * context remembers the frame and the range the set was built from; a later call replaces the set, range included.  Memory:
+ * 2 * count * (N^2 - 1) / 3 * 16 bytes.  ocean_build_mips and its buffers are independent of all this.
+ * ocean_read_mips_tile copies one tile's chains out (synchronises; ocean_mip_texels(N) float4 each; either pointer may be NULL).
+ * ocean_device_mips_tiles hands out the pointers (NULL while there is no set), the built range and the number of levels (log2 N).
+ * Errors: OCEAN_E_INVALID for a NULL context, count == 0, a range or tile outside the batch; OCEAN_E_NOT_READY without Prepare or frame,
+ * and for the read also without a set (none built since the last ocean_prepare or tile size) or for a tile outside the built range.   */
+int ocean_build_mips_tiles(ocean_t* ctx, uint32_t first_tile, uint32_t count);
+int ocean_read_mips_tile(ocean_t* ctx, uint32_t tile, float* disp_mips, float* nrm_mips);
+int ocean_device_mips_tiles(ocean_t* ctx, void** d_disp_mips, void** d_nrm_mips,
+                            uint32_t* first_tile, uint32_t* count, uint32_t* levels);
+
 /* ---- surface query: displaced height and normal at arbitrary points --------------------------------------------------
  * What gameplay / physics code asks of an ocean (buoys, boats, cameras kept above the water): how high is the water at
  * world point (x, z), and which way does it face.  The surface is the one ocean_displace_grid_cascades draws (one tile:
@@ -98,6 +116,52 @@ int ocean_query_surface(ocean_t* ctx, const ocean_surface* s, const float* xz, u
                         float* out_pos, float* out_nrm);
 int ocean_query_surface_device(ocean_t* ctx, const ocean_surface* s, const void* d_xz, uint32_t points,
                                void* d_out_pos, void* d_out_nrm);
+
+/* ---- LOD sampling: the surface at the level that fits the caller's mesh (the reference's to-do "LOD. anti-aliasing") -----------
+ * A mesh whose vertex spacing exceeds a cascade's texel spacing (uv_scale * N / grid_size > 1: a far-field ring, a coarse grid)
+ * aliases when it samples level 0.  These calls read each cascade's maps at the mip level that fits a footprint f, the spacing of the
+ * caller's mesh at that vertex in mesh metres -- a clipmap ring's cell size, a projected grid's distance to its neighbours; the
+ * library does not dictate the topology.
+ * ocean_sample_surface_lod is the FORWARD evaluation: what the cascade vertex stage would write for a vertex at rest point (x, z).
+ * It is not the Newton inverse of ocean_query_surface; s->iterations is ignored.  fp32 throughout, no contraction, in this order
+ * (tests/lod.py repeats it step for step):
+ *   texels per metre (host)   tpm_c = fabsf((uv_scales[c] * (float)N) / ((float)grid_size * vertex_distance))
+ *   ratio                     rho = (f * l->scale) * tpm_c
+ *   level                     Lmax = log2 N, or min(log2 N, max_level) where max_level != 0
+ *                             !(rho > 1.0f)    -> lev = 0, t = 0           (0, negative, NaN)
+ *                             rho >= 2^Lmax    -> lev = Lmax, t = 0        (+inf)
+ *                             otherwise        -> lev = the unbiased exponent of rho, t = ldexpf(rho, -lev) - 1.0f   (both exact)
+ *                             (between two levels the blend is linear in rho, not in log2 rho)
+ *   sample                    (u, v) as ocean_query_surface forms them from a rest point; us = u * uv_scales[c], vs likewise;
+ *                             A = the LINEAR, REPEAT sample of level lev (extent N >> lev; level 0 is the map, levels >= 1 the set of
+ *                             ocean_build_mips_tiles); t == 0 -> A, the upper level is not read; otherwise B = the same sample of
+ *                             level lev + 1, it = 1.0f - t, each channel A*it + B*t.  Both maps of a cascade use the same (lev, t).
+ *   combine                   as ocean_displace_grid_cascades: sums in cascade order from 0.0f, dy += D.y * A_c, w = fminf from FLT_MAX
+ *   out_pos = (x + dx, 0.0f + dy, z + dz, w)
+ *   out_nrm = (n.x, n.y, n.z, lambda),  lambda = fmaxf over the cascades, from 0.0f, of (float)lev + t: the coarsest level that went
+ *             into the vertex, for the caller's own blending.
+ * Readiness: the set of ocean_build_mips_tiles must cover first_tile .. first_tile+cascades-1 and must have been built from the frame
+ * the call reads, the most recently enqueued one -- otherwise OCEAN_E_NOT_READY, also when every point would stay on level 0.  A new
+ * frame, ocean_prepare or ocean_set_tile_size makes the set stale: rebuild it once per frame, behind the frame.
+ * Other errors, supported range, staging, stream order and fault rule as ocean_query_surface / _device; additionally OCEAN_E_INVALID for a
+ * NULL l or a scale that is not finite and positive.  points == 0 returns OCEAN_OK before the pointers are looked at.  The host form
+ * stages [outputs | 12-byte inputs] in the context's buffer; the device form needs 4-byte-aligned input, 16-byte-aligned outputs.
+ * ocean_displace_grid_lod is ocean_displace_grid_cascades with every sample taken through this sampler at f = fabsf(vertex_distance):
+ * the same vertices, (u, v), output buffers and read-out (ocean_read_grid, ocean_device_grid), normals.w = 0.0f.  Where no cascade is
+ * undersampled (rho <= 1 for all) it equals ocean_displace_grid_cascades in every bit.  Errors: those of that call and those above.
+ * (An addition to ABI version 5.)                                                                                                    */
+typedef struct ocean_lod {
+    float    scale;        /* multiplies every footprint; > 0 and finite          default 1 */
+    uint32_t max_level;    /* highest level used; 0 = no limit (log2 N)           default 0 */
+} ocean_lod;
+void ocean_default_lod(ocean_lod* l);
+int ocean_sample_surface_lod(ocean_t* ctx, const ocean_surface* s, const ocean_lod* l,
+                             const float* xzf /* 3 * points: x, z, footprint in mesh metres */, uint32_t points,
+                             float* out_pos /* 4 * points */, float* out_nrm /* 4 * points */);
+int ocean_sample_surface_lod_device(ocean_t* ctx, const ocean_surface* s, const ocean_lod* l,
+                                    const void* d_xzf, uint32_t points, void* d_out_pos, void* d_out_nrm);
+int ocean_displace_grid_lod(ocean_t* ctx, uint32_t first_tile, uint32_t count, uint32_t grid_size, float vertex_distance,
+                            const float* uv_scales /* count */, float choppy, const ocean_lod* l);
 
 /* ---- ray cast: where a ray first meets the water --------------------------------------------------------------------
  * Camera picking, projectiles and splashes, line of sight over the waves, a camera's near plane kept out of a crest, "is the

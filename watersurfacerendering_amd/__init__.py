@@ -543,6 +543,80 @@ class OceanBatch:
             off += w * w; w //= 2
         return out_d, out_q
 
+    # -- LOD sampling (include/ocean_consumers.h: ocean_build_mips_tiles, ocean_sample_surface_lod, ocean_displace_grid_lod) -----
+    def build_mips_tiles(self, first_tile: int = 0, count: Optional[int] = None):
+        """Mip chains of both maps of the tiles first_tile .. first_tile+count-1 (default: to the end of the batch) behind the most
+        recent frame (ocean_build_mips_tiles): the set the LOD calls read.  Enqueued on the frame's stream; returns at once."""
+        n = self.tiles - int(first_tile) if count is None else int(count)
+        _abi.check(self._L.ocean_build_mips_tiles(self._h, int(first_tile), n), "ocean_build_mips_tiles")
+
+    def read_mips_tile(self, tile: int):
+        """One tile's chains of the set (ocean_read_mips_tile; synchronises): (disp_levels, nrm_levels) as build_mips returns them."""
+        texels = int(self._L.ocean_mip_texels(self.tile_size))
+        d = np.empty((texels, 4), dtype=np.float32)
+        q = np.empty_like(d)
+        _abi.check(self._L.ocean_read_mips_tile(self._h, int(tile), d.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p)),
+                   "ocean_read_mips_tile")
+        out_d, out_q, off, w = [], [], 0, self.tile_size // 2
+        while w >= 1:
+            out_d.append(d[off:off + w * w].reshape(w, w, 4)); out_q.append(q[off:off + w * w].reshape(w, w, 4))
+            off += w * w; w //= 2
+        return out_d, out_q
+
+    def device_mips_tiles(self):
+        """(d_disp_mips, d_nrm_mips, first_tile, count, levels) of the set (ocean_device_mips_tiles); the pointers are None without one."""
+        d, q = C.c_void_p(), C.c_void_p()
+        first, count, levels = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _abi.check(self._L.ocean_device_mips_tiles(self._h, C.byref(d), C.byref(q), C.byref(first), C.byref(count), C.byref(levels)),
+                   "ocean_device_mips_tiles")
+        return d.value, q.value, first.value, count.value, levels.value
+
+    @staticmethod
+    def _lod(scale, max_level) -> "_abi.Lod":
+        l = _abi.Lod()
+        l.scale, l.max_level = float(scale), int(max_level)
+        return l
+
+    def sample_surface_lod(self, xzf, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                           vertex_distance: Optional[float] = None, choppy: float = -1.0, scale: float = 1.0, max_level: int = 0):
+        """What the cascade vertex stage would write for vertices at the rest points xzf [points, 3] = (x, z, footprint in mesh metres),
+        every cascade read at the mip level that fits its footprint (ocean_sample_surface_lod; needs build_mips_tiles behind the
+        most recent frame).  Returns (pos, nrm), each (points, 4) float32: pos = (x + dx, height, z + dz, smallest Jacobian slot),
+        nrm = (unit normal, coarsest level used)."""
+        q = np.ascontiguousarray(xzf, dtype=np.float32).reshape(-1, 3)
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, 0)
+        l = self._lod(scale, max_level)
+        pos = np.empty((q.shape[0], 4), dtype=np.float32)
+        nrm = np.empty_like(pos)
+        _abi.check(self._L.ocean_sample_surface_lod(self._h, C.byref(s), C.byref(l), q.ctypes.data_as(C.c_void_p), q.shape[0],
+                                                    pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)), "ocean_sample_surface_lod")
+        return pos, nrm
+
+    def sample_surface_lod_device(self, d_xzf: int, points: int, d_pos: int, d_nrm: int, first_tile: int = 0, uv_scales=(1.0,),
+                                  grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0,
+                                  scale: float = 1.0, max_level: int = 0):
+        """sample_surface_lod on device arrays of the context's device (ocean_sample_surface_lod_device): d_xzf [points][3], d_pos /
+        d_nrm [points][4] float32, 16-byte aligned.  Enqueued on the frame's stream (`stream`); returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, 0)
+        l = self._lod(scale, max_level)
+        _abi.check(self._L.ocean_sample_surface_lod_device(self._h, C.byref(s), C.byref(l), C.c_void_p(d_xzf), int(points), C.c_void_p(d_pos),
+                                                           C.c_void_p(d_nrm)), "ocean_sample_surface_lod_device")
+
+    def displace_grid_lod(self, uv_scales, first_tile: int = 0, grid_size: Optional[int] = None,
+                          vertex_distance: Optional[float] = None, choppy: float = -1.0, scale: float = 1.0, max_level: int = 0):
+        """displace_grid_cascades with every cascade read at the mip level that fits the grid's vertex spacing (ocean_displace_grid_lod;
+        needs build_mips_tiles behind the most recent frame): returns (positions, normals) like displace_grid."""
+        sc = np.ascontiguousarray(uv_scales, dtype=np.float32)
+        g = self.tile_size if grid_size is None else int(grid_size)
+        vd = (1000.0 / 512.0) if vertex_distance is None else float(vertex_distance)
+        l = self._lod(scale, max_level)
+        _abi.check(self._L.ocean_displace_grid_lod(self._h, first_tile, sc.size, g, vd, sc.ctypes.data_as(C.POINTER(C.c_float)), choppy,
+                                                   C.byref(l)), "ocean_displace_grid_lod")
+        pos = np.empty(((g + 1) * (g + 1), 4), dtype=np.float32)
+        nrm = np.empty_like(pos)
+        _abi.check(self._L.ocean_read_grid(self._h, pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)), "ocean_read_grid")
+        return pos, nrm
+
     def export_maps(self):
         """dma-buf of the current map set (ocean_export_maps): (fd, disp_offset, nrm_offset, bytes, map_set); close the fd yourself."""
         fd, ms = C.c_int(-1), C.c_int(0)

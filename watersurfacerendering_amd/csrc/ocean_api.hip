@@ -695,6 +695,7 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
     c->seed = seed;
     c->prepared = true;
     c->have_frame = false;
+    c->lod_ready = false;                       // (the mip set of ocean_build_mips_tiles belongs to a frame of the old spectrum)
     if (c->fault) *c->fault = 0u;
     return placement_search(c);
 }
@@ -858,6 +859,7 @@ static int enqueue_frame(ocean_ctx* c, FrameRequest& rq)
     c->launch_count = fl.launch_count;
     for (int l = 0; l < fl.launch_count; ++l) c->launch_kernel[l] = fl.launch_kernel[l];
     if (pipe && !redo) c->frame_ctr++;
+    c->frame_serial++;                              // (a re-enqueued frame counts too: what was built behind the faulted one is stale)
     c->have_frame = true;
     c->last_set = set;
     return OCEAN_OK;

@@ -47,6 +47,40 @@ __device__ __forceinline__ float4 sample_linear_repeat(const float4* __restrict_
                        mix(t00.z, t10.z, t01.z, t11.z), mix(t00.w, t10.w, t01.w, t11.w));
 }
 
+// LOD (include/ocean_consumers.h: ocean_sample_surface_lod): the level that fits a footprint of rho texels and the blend towards the next one.
+// rho <= 1 (and 0, negative, NaN) stays on the map itself; rho >= top = 2^Lmax sits on the last level; in between lev = floor(log2 rho) is
+// rho's exponent field and t = rho / 2^lev - 1 its mantissa, both exact -- the blend is linear in rho, so no log2f whose bits the tests'
+// numpy restatement (tests/lod.py: np.frexp) could not repeat.
+__device__ __forceinline__ void lod_level(float rho, int lmax, float top, int& lev, float& t)
+{
+    lev = 0; t = 0.0f;
+    if (!(rho > 1.0f)) return;
+    if (rho >= top) { lev = lmax; return; }
+    const unsigned bits = __float_as_uint(rho);                        // positive, normal: 1 < rho < 2^12
+    lev = (int)(bits >> 23) - 127;
+    t = __uint_as_float((bits & 0x007fffffu) | 0x3f800000u) - 1.0f;    // ldexpf(rho, -lev) - 1
+}
+
+// Level l of a tile: the map itself, or its place in the tile's packed chain (l >= 1 starts at texel sum_{k=1}^{l-1} (n >> k)^2).
+__device__ __forceinline__ const float4* lod_level_ptr(const float4* __restrict__ map, const float4* __restrict__ chain, int n, int l)
+{
+    if (l == 0) return map;
+    const unsigned n2 = (unsigned)n * (unsigned)n, m = (unsigned)n >> (l - 1);
+    return chain + (n2 - m * m) / 3u;
+}
+
+// The trilinear sample: sample_linear_repeat on level lev (extent n >> lev; the 1 x 1 level works with the same index masks) and, where
+// t != 0, on level lev + 1, blended A * (1 - t) + B * t per channel.  t == 0 never reads the upper level.
+__device__ __forceinline__ float4 sample_lod(const float4* __restrict__ map, const float4* __restrict__ chain, int n, int lev, float t, float u, float v)
+{
+#pragma clang fp contract(off)
+    const float4 a = sample_linear_repeat(lod_level_ptr(map, chain, n, lev), n >> lev, u, v);
+    if (t == 0.0f) return a;
+    const float4 b = sample_linear_repeat(lod_level_ptr(map, chain, n, lev + 1), n >> (lev + 1), u, v);
+    const float it = 1.0f - t;
+    return make_float4(a.x * it + b.x * t, a.y * it + b.y * t, a.z * it + b.z * t, a.w * it + b.w * t);
+}
+
 __global__ void k_displace_grid(const GridArgs g)
 {
 #pragma clang fp contract(off)

@@ -1,11 +1,12 @@
 // ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
-// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity) and the device memory those calls own.  Their kernels:
-// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling) and the device memory those calls own.  Their kernels:
+// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
 #include <cmath>
 
 #include "ocean_ctx.h"
 #include "ocean_foam_kernels.h"     // (includes ocean_consumer_kernels.h)
 #include "ocean_buoyancy_kernels.h" // (includes ocean_velocity_kernels.h)
+#include "ocean_lod_kernels.h"
 
 using namespace ocean;
 
@@ -85,9 +86,11 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     // the grid and mip buffers survive a new tile size (the grid's does not depend on it, ocean_build_mips re-allocates for mips_n != n),
     // their contents do not: they were made from maps that are gone
     c->mips_ready = false; c->grid_vertices = 0;
+    c->lod_ready = false;           // (the set of ocean_build_mips_tiles likewise: its capacity is in texels, whatever the tile size)
     if (!everything) return;
     free_and_null(c->grid_pos); free_and_null(c->grid_nrm); c->grid_capacity = 0;
     free_and_null(c->mips_disp); free_and_null(c->mips_nrm); c->mips_n = 0;
+    free_and_null(c->lod_disp); free_and_null(c->lod_nrm); c->lod_capacity = 0;
     free_and_null(c->hull); c->hull_points = 0;
     if (c->consumer_ev) { (void)hipEventDestroy(c->consumer_ev); c->consumer_ev = nullptr; }
     c->consumer_pending = false;
@@ -382,6 +385,162 @@ int ocean_raycast_surface_device(ocean_t* c, const ocean_surface* s, const ocean
     LastFrame f;
     RaycastArgs a{};
     return device_call(c, raycast_args(c, s, r, f, a), f, a, launch_raycast, count, d_rays, d_out_hit, d_out_nrm, 2);
+}
+
+}  // extern "C"
+
+// ---- LOD sampling (include/ocean_consumers.h): mip chains of a tile range, the footprint-driven sampler's two consumers ----------------------
+static uint32_t log2_of(uint32_t n) { uint32_t l = 0; while ((1u << l) < n) ++l; return l; }
+
+// The sampler's share of the launch arguments for the cascade set first_tile .. first_tile + cascades - 1 read from frame f: the set must
+// cover the range and have been built from exactly that frame -- whatever the footprints turn out to be.
+static int lod_set_args(const ocean_ctx* c, const ocean_lod* l, const LastFrame& f, uint32_t first_tile, uint32_t cascades, const float* uv_scales,
+                        uint32_t grid_size, float vertex_distance, LodSet& s)
+{
+    if (!c->lod_ready || c->lod_frame != c->frame_serial || c->lod_set != f.set) return OCEAN_E_NOT_READY;
+    if (first_tile < c->lod_first || first_tile + cascades > c->lod_first + c->lod_count) return OCEAN_E_NOT_READY;
+    s.chain_texels = ocean_mip_texels(c->n);
+    s.mips_disp = c->lod_disp + (first_tile - c->lod_first) * s.chain_texels;
+    s.mips_nrm = c->lod_nrm + (first_tile - c->lod_first) * s.chain_texels;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i)
+        s.tpm[i] = i < cascades ? std::fabs((uv_scales[i] * (float)c->n) / ((float)grid_size * vertex_distance)) : 0.0f;
+    s.scale = l->scale;
+    const uint32_t top = log2_of(c->n);
+    s.lmax = (int)(l->max_level != 0 && l->max_level < top ? l->max_level : top);
+    s.top = (float)(1u << s.lmax);
+    return OCEAN_OK;
+}
+
+static bool lod_valid(const ocean_lod* l) { return l && l->scale > 0.0f && std::isfinite(l->scale); }
+
+// ... of the point form: the LOD settings, the surface of the query (its iterations do not matter here), then the set.
+static int lod_point_args(ocean_ctx* c, const ocean_surface* s, const ocean_lod* l, LastFrame& f, LodPointArgs& a)
+{
+    if (!c || !s || !lod_valid(l)) return OCEAN_E_INVALID;
+    ocean_surface forward = *s;
+    forward.iterations = 0;
+    OCEAN_TRY(query_args(c, &forward, f, a.q));
+    return lod_set_args(c, l, f, s->first_tile, s->cascades, s->uv_scales, s->grid_size, s->vertex_distance, a.lod);
+}
+
+static int launch_lod_points(LodPointArgs& a, uint32_t points, const void* d_xzf, void* d_out_pos, void* d_out_nrm, hipStream_t st)
+{
+    a.xzf = static_cast<const float*>(d_xzf);
+    a.q.xz = nullptr;
+    a.q.out_pos = static_cast<float4*>(d_out_pos);
+    a.q.out_nrm = static_cast<float4*>(d_out_nrm);
+    a.q.points = points;
+    hipLaunchKernelGGL(k_sample_surface_lod, dim3((a.q.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_build_mips_tiles(ocean_t* c, uint32_t first_tile, uint32_t count)
+{
+    if (!c || count == 0 || first_tile >= c->tiles || count > c->tiles - first_tile) return OCEAN_E_INVALID;
+    LastFrame f;
+    OCEAN_TRY(last_frame(c, first_tile, f));
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t n = c->n;
+    const size_t chain = ocean_mip_texels(n), need = (size_t)count * chain;
+    if (need > c->lod_capacity)
+        OCEAN_TRY(regrow(c, &c->lod_disp, &c->lod_nrm, need * sizeof(float4), c->lod_capacity, need, [c] { c->lod_ready = false; }));
+    c->lod_ready = false;           // until both launches are enqueued: a failure below leaves no set
+    MipTilesArgs m;
+    m.src[0] = f.disp; m.src[1] = f.nrm;
+    m.dst[0] = c->lod_disp; m.dst[1] = c->lod_nrm;
+    m.src_stride = f.n2; m.chain_texels = chain; m.dst_offset = 0;
+    m.sw = (int)n; m.be = n < (uint32_t)MIP_BLOCK ? (int)n : MIP_BLOCK;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    hipLaunchKernelGGL(k_mips_tiles, dim3((n / m.be) * (n / m.be), 2, count), dim3(256), 0, f.st, m);
+    if (n > (uint32_t)MIP_BLOCK) {  // levels 7 .. log2 N from level 6 of the chains: one block per map and tile
+        size_t level6 = 0;
+        for (uint32_t k = 1; k < 6; ++k) level6 += (size_t)(n >> k) * (n >> k);
+        m.src[0] = c->lod_disp + level6; m.src[1] = c->lod_nrm + level6;
+        m.src_stride = chain;
+        m.sw = m.be = (int)(n / MIP_BLOCK);
+        m.dst_offset = level6 + (size_t)m.sw * m.sw;
+        hipLaunchKernelGGL(k_mips_tiles, dim3(1, 2, count), dim3(256), 0, f.st, m);
+    }
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->lod_first = first_tile; c->lod_count = count;
+    c->lod_frame = c->frame_serial; c->lod_set = f.set;
+    c->lod_ready = true;
+    return OCEAN_OK;
+}
+
+int ocean_read_mips_tile(ocean_t* c, uint32_t tile, float* disp_mips, float* nrm_mips)
+{
+    if (!c || tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!c->prepared || !c->have_frame || !c->lod_ready || tile < c->lod_first || tile - c->lod_first >= c->lod_count) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    const size_t chain = ocean_mip_texels(c->n), at = (tile - c->lod_first) * chain;
+    if (disp_mips) HIP_TRY(hipMemcpy(disp_mips, c->lod_disp + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
+    if (nrm_mips) HIP_TRY(hipMemcpy(nrm_mips, c->lod_nrm + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+int ocean_device_mips_tiles(ocean_t* c, void** d_disp_mips, void** d_nrm_mips, uint32_t* first_tile, uint32_t* count, uint32_t* levels)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (d_disp_mips) *d_disp_mips = c->lod_ready ? c->lod_disp : nullptr;
+    if (d_nrm_mips) *d_nrm_mips = c->lod_ready ? c->lod_nrm : nullptr;
+    if (first_tile) *first_tile = c->lod_ready ? c->lod_first : 0;
+    if (count) *count = c->lod_ready ? c->lod_count : 0;
+    if (levels) *levels = c->lod_ready ? log2_of(c->n) : 0;
+    return OCEAN_OK;
+}
+
+void ocean_default_lod(ocean_lod* l)
+{
+    if (!l) return;
+    l->scale = 1.0f;
+    l->max_level = 0;
+}
+
+int ocean_sample_surface_lod(ocean_t* c, const ocean_surface* s, const ocean_lod* l, const float* xzf, uint32_t points,
+                             float* out_pos, float* out_nrm)
+{
+    LastFrame f;
+    LodPointArgs a{};
+    return staged_call(c, lod_point_args(c, s, l, f, a), f, a, launch_lod_points, points, xzf, 3, out_pos, out_nrm, 2);
+}
+
+int ocean_sample_surface_lod_device(ocean_t* c, const ocean_surface* s, const ocean_lod* l, const void* d_xzf, uint32_t points,
+                                    void* d_out_pos, void* d_out_nrm)
+{
+    LastFrame f;
+    LodPointArgs a{};
+    return device_call(c, lod_point_args(c, s, l, f, a), f, a, launch_lod_points, points, d_xzf, d_out_pos, d_out_nrm, 2);
+}
+
+int ocean_displace_grid_lod(ocean_t* c, uint32_t first_tile, uint32_t count, uint32_t grid_size, float vertex_distance,
+                            const float* uv_scales, float choppy, const ocean_lod* l)
+{
+    if (!c || !uv_scales || count == 0 || count > (uint32_t)OCEAN_MAX_CASCADES || first_tile >= c->tiles || first_tile + count > c->tiles ||
+        grid_size == 0 || grid_size > 8192 || !lod_valid(l))
+        return OCEAN_E_INVALID;
+    LastFrame f;
+    LodGridArgs a{};
+    uint32_t verts;
+    // readiness is settled before the grid's buffers may be re-allocated (a refused call leaves the previous grid readable), and once more
+    // behind that: a re-allocation drains the context, and a frame it had to run again is a new frame
+    OCEAN_TRY(last_frame(c, first_tile, f));
+    OCEAN_TRY(lod_set_args(c, l, f, first_tile, count, uv_scales, grid_size, vertex_distance, a.lod));
+    OCEAN_TRY(grid_args(c, first_tile, grid_size, vertex_distance, 1.0f, choppy, f, a.a.g, verts));
+    OCEAN_TRY(lod_set_args(c, l, f, first_tile, count, uv_scales, grid_size, vertex_distance, a.lod));
+    a.a.count = (int)count; a.a.tile_texels = f.n2;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) a.a.uv_scale[i] = i < count ? uv_scales[i] : 0.0f;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    hipLaunchKernelGGL(k_displace_grid_lod, dim3((verts + 255) / 256), dim3(256), 0, f.st, a);
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->grid_vertices = verts;
+    return OCEAN_OK;
 }
 
 }  // extern "C"

@@ -184,7 +184,17 @@ struct ocean_ctx {
     float4* mips_nrm = nullptr;
     uint32_t mips_n = 0;            // tile size the two buffers were allocated for
     bool mips_ready = false;
-    std::vector<float> prep_length;         // [tiles] tile length the most recent ocean_prepare built the spectrum for
+    // Mip chains of a tile range (ocean_build_mips_tiles): [lod_count][ocean_mip_texels(N)] per map, each tile in the packed layout above.
+    // What the LOD sampler reads, so the set remembers the frame it was built from: a consumer of another frame finds it stale.
+    float4* lod_disp = nullptr;
+    float4* lod_nrm = nullptr;
+    size_t lod_capacity = 0;        // texels per buffer
+    uint32_t lod_first = 0, lod_count = 0;  // the built range [lod_first, lod_first + lod_count)
+    uint64_t lod_frame = 0;         // frame_serial and chain of the frame the set was built from
+    int lod_set = 0;
+    bool lod_ready = false;         // a set has been built since the last ocean_prepare / new tile size
+    uint64_t frame_serial = 0;      // successful frame enqueues of the context's whole life (never reset: no two frames share a number)
+    std::vector<float> prep_length;        // [tiles] tile length the most recent ocean_prepare built the spectrum for
     std::vector<float> set_lambda[MAXD];    // [tiles] lambda and tile length of the frame that wrote each chain's maps
     std::vector<float> set_length[MAXD];    //   (recorded when it is enqueued: what ocean_query_surface's Newton step needs)
     // Staging of the host-blocking consumer calls (ocean_query_surface, ocean_raycast_surface, ocean_query_foam): [float4 outputs | input] of
