@@ -1126,6 +1126,73 @@ __device__ __forceinline__ void for_each_output(int tid, F f)
     }
 }
 
+// ---- whole 64-byte pieces from the MIRRORED map rows ------------------------------------------------------------------------------
+// A map workgroup stores texel (q, p) and its point mirror (N - q, (N - p) & (N - 1)).  With a wave on positions p = 64 k .. 64 k + 63 the
+// mirrored store covers columns N - 64 k - 63 .. N - 64 k: 1 KiB that starts 16 bytes past a 1 KiB boundary, so both boundary pieces reach
+// the memory side as byte-masked requests of two different waves -- and a masked request is far dearer than a whole one
+// (tools/ubench/fillbw.hip `shapes`, profiles/whole_piece_stores.txt).  Here the lane on position p stores the mirror of position p + 1
+// instead (cyclically along the row: the value of p = 0 lands at the row's end), to column N - 1 - p: the wave covers N - 64 k - 64 ..
+// N - 64 k - 1, whole pieces only, and every mirrored texel is still written exactly once with the same bits.  Inside a wave the value
+// comes from the next lane (a DPP wave rotate); the last lane takes it from lane 0 of the wave on the next 64 positions, which published
+// it in a small LDS region of its own (one float4 per row and 64 positions; one barrier between publishing and the mirrored stores).
+// Only where the last stage hands a wave 64 consecutive positions of ONE row and every thread has the same number of outputs
+// (last_stage_map, LM = 1: 512^2 up); smaller tiles, whose rows end inside a wave, keep storing the mirror of their own position.
+// And only in the streamed form (NTS): plain stores that land in the memory-side cache take a masked request at the price of a whole one
+// (fillbw: 0.99-1.00), while a serial frame's x pass -- one round of workgroups that ends in its store burst -- pays for every texel
+// held back to the barrier (all forms rotated: k_xpass_disp 16.6 -> 18.5-19.3 us, k_xpass_b 19.9 -> 21.5 serial at 2048^2).  Pipelined
+// frames and big batches, whose maps go out non-temporally, gain (2048^2 depth 3: 46.6 -> 45.4 us per frame).
+template <int N, int C, int T, class P, int LM, bool NTS = true> constexpr bool mirror_rotates()
+{
+    return NTS && LM == 1 && C > 1 && (N / P::last) % 64 == 0 && T % 64 == 0 && ((N / P::last) * C) % T == 0;
+}
+// bytes of the hand-off region behind an x-pass workgroup's other LDS (0 where the mirror does not rotate)
+template <int N, int C, int T, class P> constexpr size_t mirror_handoff_bytes() { return mirror_rotates<N, C, T, P, 1>() ? sizeof(float4) * C * (N / 64) : 0; }
+// where it starts: behind the FFT image and the HEIGHT role's per-wave min / max, 16-byte aligned
+template <int N, int C, int T> constexpr size_t mirror_handoff_offset() { return (sizeof(c32) * fft_lds_elems<N, C>() + sizeof(float) * 2 * ((T + 63) / 64) + 15) / 16 * 16; }
+// this lane's value of the next lane, lane 63's of lane 0 (wave_rol:1; every lane of the wave must be active)
+__device__ __forceinline__ float wave_next_lane(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x134, 0xf, 0xf, false));
+}
+// First: lane 0's texel of each run of 64 positions, published for the wave on the 64 positions before it (value(p, q, u, i) -> float4).
+template <int N, class LS, int T, class V>
+__device__ __forceinline__ void publish_row_heads(float4* hand, int tid, int u0, V value)
+{
+    for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) {
+        if ((tid & 63) == 0) hand[c * (N / 64) + (p >> 6)] = value(p, u0 + c, u, i);
+    });
+}
+// Then, behind the workgroup's barrier, output by output: texel (q, p), and the mirror of position p + 1 to (N - q, N - 1 - p).
+// side(p, q, o): whatever else goes with a valid texel.  `value` must give the bits it gave above.
+template <int N, class LS, int T, bool NTS, class V, class S, class M>
+__device__ __forceinline__ void store_rows_whole(float4* __restrict__ map, float4* __restrict__ map_host, const float4* hand, int tid, int u0, V value, S side, M mirror)
+{
+    __syncthreads();
+    for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) {
+        const int q = u0 + c;
+        const float4 o = value(p, q, u, i);
+        float4 nx = make_float4(wave_next_lane(o.x), wave_next_lane(o.y), wave_next_lane(o.z), wave_next_lane(o.w));
+        if ((tid & 63) == 63) nx = hand[c * (N / 64) + (((p >> 6) + 1) & (N / 64 - 1))];
+        if (q > N / 2) return;                                      // padding row
+        side(p, q, o);
+        store_map<NTS>(map, (unsigned)(q * N + p), o);
+        store_map_host(map_host, (unsigned)(q * N + p), o);
+        if (q == 0 || q == N / 2) return;                           // rows 0 and N/2 are their own mirrors
+        const unsigned t = (unsigned)((N - q) * N + (N - 1 - p));
+        const float4 m = mirror(nx);
+        store_map<NTS>(map, t, m);
+        store_map_host(map_host, t, m);
+    });
+}
+// keeps the compiler from carrying the published pass's texels (four registers each) over the barrier instead of the two they are made of
+template <int A, int B> __device__ __forceinline__ void launder(c32 (&x)[A][B])
+{
+#pragma unroll
+    for (int u = 0; u < A; ++u)
+#pragma unroll
+        for (int i = 0; i < B; ++i) asm volatile("" : "+v"(x[u][i].x), "+v"(x[u][i].y));
+}
+
 // ============================================================================
 // x pass (second pass, x axis), two launches:
 //   k_xpass_b    blockIdx.x < HB  -> HEIGHT workgroup: 2*C rows of the height (C transforms of
@@ -1360,15 +1427,22 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     [[maybe_unused]] float* __restrict__ jac0 = JAC ? a.jac0 + (size_t)tile * HF::HRAW_TILE : nullptr;
     [[maybe_unused]] const float lambda = a.lambda ? a.lambda[tile] : a.lambda_all;
     c32 held[LS::IT][LS::RL];
-    auto emit = [&](int p, int c, c32 slopes, c32 derivs) {
+    auto texel = [&](int p, int q, c32 slopes, c32 derivs) -> float4 {
 #pragma clang fp contract(off)          // every instantiation of this kernel rounds alike: frames are bit-identical whichever one a launch picks
-        const int q = u0 + c;
-        if (q > N / 2) return;                                      // padding row
         const float s = ((p + q) & 1) ? -1.0f : 1.0f;
         // (slope x, slope z, dDx/dx, dDz/dz) * sign   (.cpp:430-435)
-        const float4 o = make_float4(s * slopes.x, s * slopes.y, s * derivs.x, s * derivs.y);
+        return make_float4(s * slopes.x, s * slopes.y, s * derivs.x, s * derivs.y);
+    };
+    auto jac_factor = [&]([[maybe_unused]] int p, [[maybe_unused]] int q, [[maybe_unused]] float4 o) {
+#pragma clang fp contract(off)
         if constexpr (JAC)          // (1 + lambda s dxDx)(1 + lambda s dzDz) of .cpp:423-425, finished by the displacement pass
             at32(jac0, hraw_index(N, p, q)) = (1.0f + lambda * o.z) * (1.0f + lambda * o.w);
+    };
+    auto emit = [&](int p, int c, c32 slopes, c32 derivs) {
+        const int q = u0 + c;
+        if (q > N / 2) return;                                      // padding row
+        const float4 o = texel(p, q, slopes, derivs);
+        jac_factor(p, q, o);
         OCEAN_STORE(nrm, q * N + p, o);
         store_map_host(nrm_host, (unsigned)(q * N + p), o);
         if (q != 0 && q != N / 2) {                                  // mirror: slopes odd, derivatives even
@@ -1377,6 +1451,26 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         }
     };
     const c32 zero = make_float2(0.0f, 0.0f);
+    // a full group's rows in the streamed form from 512^2 up: every output in registers first, then texel and whole-piece mirror, output by
+    // output (mirror_rotates)
+    constexpr bool ROT = mirror_rotates<N, C, T, P, LM, NTS>();
+    [[maybe_unused]] c32 held2[ROT ? LS::IT : 1][ROT ? LS::RL : 1];
+    [[maybe_unused]] auto fill = [&](auto& x, c32 v) {
+#pragma unroll
+        for (int u = 0; u < LS::IT; ++u)
+#pragma unroll
+            for (int i = 0; i < LS::RL; ++i) x[u][i] = v;
+    };
+    [[maybe_unused]] auto store_rows = [&]() {
+        if constexpr (ROT) {
+            float4* hand = reinterpret_cast<float4*>(smem + mirror_handoff_offset<N, C, T>());
+            auto value = [&](int p, int q, int u, int i) { return texel(p, q, held[u][i], held2[u][i]); };
+            publish_row_heads<N, LS, T>(hand, tid, u0, value);
+            launder(held);
+            launder(held2);
+            store_rows_whole<N, LS, T, NTS>(nrm, nrm_host, hand, tid, u0, value, jac_factor, [](float4 o) { return make_float4(-o.x, -o.y, o.z, o.w); });      // slopes odd, derivatives even
+        }
+    };
     if constexpr (xpass_single_row_group<N, C>()) {
         if (u0 == N / 2) {           // the group of row N/2: one useful row, one interleaved column per transform
             using LS1 = LastStage<N, 1, T, P, LM>;
@@ -1404,7 +1498,8 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         }
     }
     if (a.mode == 2) {               // HEIGHT1: the normal map is all zero
-        for_each_output<LS, T>(tid, [&](int p, int c, int, int) { emit(p, c, zero, zero); });
+        if constexpr (ROT) { fill(held, zero); fill(held2, zero); store_rows(); }
+        else for_each_output<LS, T>(tid, [&](int p, int c, int, int) { emit(p, c, zero, zero); });
         return;
     }
     // From 2048 up this role runs one workgroup per CU whatever it does below 256 VGPRs, so the
@@ -1438,21 +1533,25 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         batch_fft<N, C, T, P>(fbuf, twr, tid, in, out);
     }
     if (a.mode == 1) {               // CHOPPY5: slopes only
-        for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) { emit(p, c, held[u][i], zero); });
+        if constexpr (ROT) { fill(held2, zero); store_rows(); }
+        else for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) { emit(p, c, held[u][i], zero); });
         return;
     }
+    auto out = [&](int p, int c, c32 v, int u, int i) {
+        if constexpr (ROT) held2[u][i] = v;
+        else emit(p, c, held[u][i], v);
+    };
     if constexpr (PREFETCH) {
         auto in = [&](int, int, int u, int i) -> c32 { return xb[u][i]; };
-        auto out = [&](int p, int c, c32 v, int u, int i) { emit(p, c, held[u][i], v); };
         batch_fft<N, C, T, P>(fbuf, twr, tid, in, out);
     } else {
         // keep the second transform's loads from being hoisted over the first one's last
         // stage: that costs ~45 VGPRs and with them the second workgroup per CU
         __builtin_amdgcn_sched_barrier(0);
         auto in = [&](int nf, int c, int, int) -> c32 { return load_pair_column<N, Z16>(z2, nf, u0 + c, 1.0f, uk); };
-        auto out = [&](int p, int c, c32 v, int u, int i) { emit(p, c, held[u][i], v); };
         batch_fft<N, C, T, P>(fbuf, twr, tid, in, out);
     }
+    store_rows();
     };
     // ---- DISP workgroup of a merged x pass (xb_disp; never in the Jacobian mode): pair 0 -> displacement-map rows u0 .. u0+C-1, like
     // k_xpass_disp, in the SAME launch as the HEIGHT workgroups whose rows and min / max it needs.  It transforms at once and holds the
@@ -1593,17 +1692,21 @@ __global__ void __launch_bounds__(T, (T == 512 ? 4 : 1)) k_xpass_disp(const Fram
         const float inv_a = 1.0f / fmaxf(fabsf(mn), fabsf(mx));
         const float lambda = a.lambda ? a.lambda[tile] : a.lambda_all;
         auto in = [&](int nf, int c, int, int) -> c32 { return load_pair_column<N, Z16>(z0, nf, u0 + c, -1.0f, uu); };
-        auto out = [&](int p, int c, c32 v, int u, int i) {
+        auto texel = [&](int p, int q, c32 v, int u, int i) -> float4 {
 #pragma clang fp contract(off)          // as in k_xpass_b
-            const int q = u0 + c;
-            if (q > N / 2) return;
             const float s = ((p + q) & 1) ? -1.0f : 1.0f;
             float w = 1.0f;
             if constexpr (JAC) {        // (1 + l s dxDx)(1 + l s dzDz) - (l s dxDz)(l s dzDx), .cpp:422-426 (the two cross terms are one field)
                 const float cross = lambda * jv[u][i];
                 w = j0[u][i] - cross * cross;
             }
-            const float4 o = make_float4(s * lambda * v.x, hv[u][i] * inv_a, s * lambda * v.y, w);
+            return make_float4(s * lambda * v.x, hv[u][i] * inv_a, s * lambda * v.y, w);
+        };
+        auto out = [&](int p, int c, c32 v, int u, int i) {
+            const int q = u0 + c;
+            if (q > N / 2) return;
+            const float4 o = texel(p, q, v, u, i);
+            const float w = o.w;
             OCEAN_STORE(disp, q * N + p, o);
             store_map_host(disp_host, (unsigned)(q * N + p), o);
             if (q != 0 && q != N / 2) {     // mirror: the displacements are odd, height and Jacobian even
@@ -1611,7 +1714,20 @@ __global__ void __launch_bounds__(T, (T == 512 ? 4 : 1)) k_xpass_disp(const Fram
                 store_map_host(disp_host, (unsigned)((N - q) * N + ((N - p) & (N - 1))), make_float4(-o.x, o.y, -o.z, w));
             }
         };
-        if (a.mode == 2)                 // HEIGHT1: no horizontal displacement, no transform
+        if constexpr (mirror_rotates<N, CC, T, P, LM, NTS>()) {
+            // every output in registers first; then texel and whole-piece mirror, output by output (mirror_rotates)
+            c32 vh[LS::IT][LS::RL];
+            auto hold = [&](int, int, c32 v, int u, int i) { vh[u][i] = v; };
+            if (a.mode == 2)             // HEIGHT1: no horizontal displacement, no transform
+                for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) { hold(p, c, make_float2(0.0f, 0.0f), u, i); });
+            else
+                batch_fft<N, CC, T, P>(fbuf, twr, tid, in, hold);
+            float4* hand = reinterpret_cast<float4*>(smem + mirror_handoff_offset<N, C, T>());
+            auto value = [&](int p, int q, int u, int i) { return texel(p, q, vh[u][i], u, i); };
+            publish_row_heads<N, LS, T>(hand, tid, u0, value);
+            launder(vh);
+            store_rows_whole<N, LS, T, NTS>(disp, disp_host, hand, tid, u0, value, [](int, int, float4) {}, [](float4 o) { return make_float4(-o.x, o.y, -o.z, o.w); });    // displacements odd, height and Jacobian even
+        } else if (a.mode == 2)          // HEIGHT1: no horizontal displacement, no transform
             for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) { out(p, c, make_float2(0.0f, 0.0f), u, i); });
         else
             batch_fft<N, CC, T, P>(fbuf, twr, tid, in, out);

@@ -41,8 +41,11 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
     constexpr size_t lds_rows = zpass_lds_bytes<N, 1>();
     constexpr bool HAS2 = zpass_has_width2<N>();
     constexpr size_t lds_rows2 = zpass_lds_bytes<N, 2>();
-    constexpr size_t lds_m = sizeof(c32) * fft_lds_elems<N, C>();
-    constexpr size_t lds_b = lds_m + sizeof(float) * 2 * ((G::T_C + 63) / 64);
+    // x passes: the FFT image (+ the HEIGHT role's per-wave min / max), and from 512^2 up the hand-off region of the mirrored rows behind both
+    constexpr size_t lds_hand = mirror_handoff_bytes<N, C, G::T_C, typename G::PC>();
+    constexpr size_t lds_m = lds_hand ? mirror_handoff_offset<N, C, G::T_C>() + lds_hand : sizeof(c32) * fft_lds_elems<N, C>();
+    constexpr size_t lds_b = lds_hand ? lds_m : sizeof(c32) * fft_lds_elems<N, C>() + sizeof(float) * 2 * ((G::T_C + 63) / 64);
+    static_assert(lds_b <= 80 * 1024, "two x-pass workgroups per compute unit");
     static_assert(HF::NUP % (2 * C) == 0, "height row blocks");
     constexpr unsigned hb_b = xpass_height_groups<N, C>(), nb = (HF::NU + C - 1) / C;
     const bool fast = !a.h0h && a.omega_q;       // the usual form of the spectrum: fp32 h0, 16-bit dispersion
