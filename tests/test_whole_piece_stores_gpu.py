@@ -135,3 +135,27 @@ def test_half2_intermediates(n):
         d, q = frame(b, depth)
         b.close()
         assert_symmetric_frame(d, q, (n, "half2", depth), own_tol=2e-3)      # half2 intermediates: 1e-3 per half
+
+
+@pytest.mark.parametrize("n", [1024, 2048])
+@pytest.mark.parametrize("mode", [1, 2, 3])
+def test_reduced_modes_streamed_equal_serial(n, mode):
+    """The streamed, rotated stores together with the modes that leave the x passes early (CHOPPY5, HEIGHT1), the Jacobian mode and the
+    single-transform group of row N/2 meet only from 1024^2 up (2048^2: the NORMAL role's register prefetch as well).  The depth-2 frame
+    is point symmetric bit for bit, and the serial frame (plain stores, own-position mirror) equals the last of two pipelined ones at the
+    same t (non-temporal stores, rotated mirror) bit for bit, maps and heights: which instantiation a launch picks changes no bit.
+    This pins path independence -- two instantiations of the same code against each other -- not accuracy: the modes are held to the
+    oracle by test_four_modes (up to 512^2) and tests/test_parity_gpu.py::test_reduced_modes_match_oracle_modes (serial)."""
+    ser = make_batch(n, depth=1, mode=mode)
+    d1, q1 = frame(ser, 1)
+    h1 = ser.heights(0)
+    ser.close()
+    pip = make_batch(n, depth=2, mode=mode)
+    d2, q2 = frame(pip, 2)
+    h2 = pip.heights(0)
+    pip.close()
+    assert_symmetric_frame(d2, q2, (n, "mode", mode, "depth 2"))
+    for name, x, y in (("displacement", d1, d2), ("normal", q1, q2)):
+        x, y = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32), np.ascontiguousarray(y, dtype=np.float32).view(np.uint32)
+        assert np.array_equal(x, y), (n, "mode", mode, name, "words that differ", int((x != y).sum()))
+    assert np.array_equal(np.float32(h1).view(np.uint32), np.float32(h2).view(np.uint32)), (n, "mode", mode, "heights", h1, h2)

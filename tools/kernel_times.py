@@ -1,6 +1,7 @@
 """Per-kernel execution times (dispatch-attached events) of serial frames, for A/B runs over variant libraries.
 usage: OCEAN_HIP_LIB=... python tools/kernel_times.py N [tiles] [frames] [h0_bits] [anim_period]
-(h0_bits 16: the fp16 spectrum; anim_period 4.0e5: dispersion multiples beyond 16 bits, i.e. the fp32 dispersion array)"""
+(h0_bits 16: the fp16 spectrum; anim_period 4.0e5: dispersion multiples beyond 16 bits, i.e. the fp32 dispersion array;
+OCEAN_Z16=1: half2 intermediates; OCEAN_MODE=0..3: the frame mode, as in depth_batch.py)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -10,10 +11,11 @@ n = int(sys.argv[1]); tiles = int(sys.argv[2]) if len(sys.argv) > 2 else 1; fram
 h0_bits = int(sys.argv[4]) if len(sys.argv) > 4 else 32; period = float(sys.argv[5]) if len(sys.argv) > 5 else None
 b = W.OceanBatch(n, tiles, 0)
 if os.environ.get('OCEAN_Z16'): b.set_intermediate_precision(16)
+if os.environ.get('OCEAN_MODE'): b.set_mode(int(os.environ['OCEAN_MODE']))
 if period is not None: b.set_params(anim_period=period)
 b.set_spectrum_precision(h0_bits)
 b.prepare(0x5EED0000)
 b.time_frames(0.0, 0.05, 200, 50, per_kernel=False)
 ms, k = b.time_frames(0.0, 0.05, 100, frames)
-print(f"N={n}x{tiles} serial {ms/frames*1e3:7.1f} us/frame   " + "  ".join(f"{nm} {v*1e3:6.2f}" for nm, v in zip(b.kernel_names(), k)))
+print(f"N={n}x{tiles} mode={os.environ.get('OCEAN_MODE', '0')} bits={16 if os.environ.get('OCEAN_Z16') else 32} serial {ms/frames*1e3:7.1f} us/frame   " + "  ".join(f"{nm} {v*1e3:6.2f}" for nm, v in zip(b.kernel_names(), k)))
 b.close()

@@ -74,7 +74,6 @@ template <bool NTS> __device__ __forceinline__ void store_map(float4* base, unsi
     if constexpr (NTS) store_nt(p, v);
     else *p = v;
 }
-#define OCEAN_STORE(base, texel, val) store_map<NTS>((base), (unsigned)(texel), (val))
 // The same texel to a SECOND destination as well: the caller's page-locked host array, through its device address (ocean_compute_waves_read,
 // small maps: FrameArgs::disp_host / nrm_host; null -- a wave-uniform branch -- in every other frame).  The x passes then write the maps
 // across PCIe as they produce them, 1 KiB per wave instruction like the device copy, instead of a copy behind the frame: a blocking 512^2
@@ -1108,6 +1107,9 @@ __device__ __forceinline__ c32 load_pair_column(const float2* __restrict__ zg, i
     const c32 v = load_z<false>(zg, HF::template zidx<Z16>(N - mf, side, u), 1.0f);
     return make_float2(eps * v.x, eps * v.y);
 }
+// Where a tile's packed intermediates start: `elems` units (float2, or half2 with Z16) behind `base` (FrameArgs::zh and z3, arrays of their own); pair 0 .. 2 of FrameArgs::z.
+template <bool Z16> __device__ __forceinline__ const float2* z_base(const float2* base, size_t elems) { return reinterpret_cast<const float2*>(reinterpret_cast<const char*>(base) + elems * (Z16 ? 4 : 8)); }
+template <int N, bool Z16> __device__ __forceinline__ const float2* pair_base(const float2* z, int tile, int pair) { return z_base<Z16>(z, (size_t)tile * Half<N>::Z_TILE + (size_t)pair * Half<N>::Z_GROUP); }
 
 // Visits the outputs (position p, column c) the LAST stage of a transform would hand to this
 // thread -- used by the reduced modes that skip a transform but still have to write its texels.
@@ -1147,8 +1149,20 @@ template <int N, int C, int T, class P, int LM, bool NTS = true> constexpr bool 
 }
 // bytes of the hand-off region behind an x-pass workgroup's other LDS (0 where the mirror does not rotate)
 template <int N, int C, int T, class P> constexpr size_t mirror_handoff_bytes() { return mirror_rotates<N, C, T, P, 1>() ? sizeof(float4) * C * (N / 64) : 0; }
-// where it starts: behind the FFT image and the HEIGHT role's per-wave min / max, 16-byte aligned
-template <int N, int C, int T> constexpr size_t mirror_handoff_offset() { return (sizeof(c32) * fft_lds_elems<N, C>() + sizeof(float) * 2 * ((T + 63) / 64) + 15) / 16 * 16; }
+// LDS of an x-pass workgroup: the FFT image | `red`, the per-wave min and max of the roles that reduce the height | 16-byte aligned, the hand-off
+// region.  For the kernels and for the host's launch sizes alike (k_xpass_disp reduces nothing, but its hand-off region sits where k_xpass_b's does).
+template <int N, int C> constexpr size_t xpass_red_offset() { return sizeof(c32) * fft_lds_elems<N, C>(); }
+template <int T> constexpr size_t xpass_red_bytes() { return sizeof(float) * 2 * ((T + 63) / 64); }
+template <int N, int C, int T> constexpr size_t mirror_handoff_offset() { return (xpass_red_offset<N, C>() + xpass_red_bytes<T>() + 15) / 16 * 16; }
+template <int N, int C, int T, class P> constexpr size_t xpass_lds_bytes(bool reduces)
+{
+    constexpr size_t hand = mirror_handoff_bytes<N, C, T, P>();
+    return hand ? mirror_handoff_offset<N, C, T>() + hand : xpass_red_offset<N, C>() + (reduces ? xpass_red_bytes<T>() : 0);
+}
+template <int N, int C, int T, class P> constexpr size_t xpass_b_lds_bytes() { return xpass_lds_bytes<N, C, T, P>(true); }
+template <int N, int C, int T, class P> constexpr size_t xpass_disp_lds_bytes() { return xpass_lds_bytes<N, C, T, P>(false); }
+template <int N, int C> __device__ __forceinline__ float* xpass_red(unsigned char* smem) { return reinterpret_cast<float*>(smem + xpass_red_offset<N, C>()); }
+template <int N, int C, int T> __device__ __forceinline__ float4* mirror_handoff(unsigned char* smem) { return reinterpret_cast<float4*>(smem + mirror_handoff_offset<N, C, T>()); }
 // this lane's value of the next lane, lane 63's of lane 0 (wave_rol:1; every lane of the wave must be active)
 __device__ __forceinline__ float wave_next_lane(float v)
 {
@@ -1192,6 +1206,21 @@ template <int A, int B> __device__ __forceinline__ void launder(c32 (&x)[A][B])
 #pragma unroll
         for (int i = 0; i < B; ++i) asm volatile("" : "+v"(x[u][i].x), "+v"(x[u][i].y));
 }
+// The mirrored texel of each map: slopes odd, the two derivatives even; displacements odd, height and Jacobian even
+struct mirror_nrm { __device__ __forceinline__ float4 operator()(float4 o) const { return make_float4(-o.x, -o.y, o.z, o.w); } };
+struct mirror_disp { __device__ __forceinline__ float4 operator()(float4 o) const { return make_float4(-o.x, o.y, -o.z, o.w); } };
+// The plain form: texel (q, p) of a valid row q <= N/2 and the mirror of ITS OWN position, to the map and to the caller's host array
+template <int N, bool NTS, class M>
+__device__ __forceinline__ void store_texel_and_mirror(float4* map, float4* map_host, int p, int q, float4 o, M mirror)
+{
+    store_map<NTS>(map, (unsigned)(q * N + p), o);
+    store_map_host(map_host, (unsigned)(q * N + p), o);
+    if (q == 0 || q == N / 2) return;                               // rows 0 and N/2 are their own mirrors
+    const unsigned t = (unsigned)((N - q) * N + ((N - p) & (N - 1)));
+    const float4 m = mirror(o);
+    store_map<NTS>(map, t, m);
+    store_map_host(map_host, t, m);
+}
 
 // ============================================================================
 // x pass (second pass, x axis), two launches:
@@ -1213,6 +1242,10 @@ template <int N, int C> constexpr bool xpass_single_row_group() { return C > 1 &
 // HEIGHT workgroups (2 C rows each: C transforms of two real rows): the groups that hold a valid row, 0 .. N/2 (round 3 also ran the
 // all-padding group behind them)
 template <int N, int C> constexpr int xpass_height_groups() { return (N / 2 + 1 + 2 * C - 1) / (2 * C); }
+// NORMAL, DISP and PAIR-3 workgroups (C map rows each)
+template <int N, int C> constexpr int xpass_row_groups() { return (Half<N>::NU + C - 1) / C; }
+// the x-axis workgroups of a tile whose HEIGHT, NORMAL and DISP roles share a launch (merged x pass, one-launch frame)
+template <int N, int C> constexpr int xpass_merged_groups() { return xpass_height_groups<N, C>() + 2 * xpass_row_groups<N, C>(); }
 
 // Completion record of a frame.  The workgroup of the frame's last launch (the displacement pass) that finishes LAST hands, per tile, one 16-byte record
 // (min key, max key, frame sequence number, 0) to host-coherent memory: a synchronous ComputeWaves returns from a short poll of
@@ -1263,6 +1296,45 @@ __device__ __forceinline__ void frame_records(const FrameArgs& a, unsigned* lds_
     }
 }
 
+// A workgroup's height extrema into the tile's two keys: wave shuffle, the waves' values through `red`, then lane 0's two atomics.
+template <int T>
+__device__ __forceinline__ void height_minmax_commit(float* red, int tid, float& vmin, float& vmax, unsigned* minmax, int tile)
+{
+    constexpr int NW = (T + 63) / 64;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        vmin = fminf(vmin, __shfl_xor(vmin, o));
+        vmax = fmaxf(vmax, __shfl_xor(vmax, o));
+    }
+    if ((tid & 63) == 0) { red[tid >> 6] = vmin; red[NW + (tid >> 6)] = vmax; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < NW; ++w) { vmin = fminf(vmin, red[w]); vmax = fmaxf(vmax, red[NW + w]); }
+        atomicMin(minmax + 2 * tile + 0, float_key(vmin));
+        atomicMax(minmax + 2 * tile + 1, float_key(vmax));
+    }
+}
+__device__ __forceinline__ float tile_lambda(const FrameArgs& a, int tile) { return a.lambda ? a.lambda[tile] : a.lambda_all; }
+// The displacement-map texel, for k_xpass_disp and the DISP role alike (the same bits): NormalizeHeights (.cpp:443-455) folded into the
+// store, from the tile's FINAL height keys.  v: pair 0 at (p, q); h: the raw signed height; jraw, jac0 (JAC): the cross derivative and
+// the NORMAL role's product (1 + l s dxDx)(1 + l s dzDz).
+template <bool JAC> struct DispTexel {
+    float inv_a, lambda;
+    __device__ __forceinline__ DispTexel(const FrameArgs& a, int tile, unsigned kmn, unsigned kmx)
+        : inv_a(1.0f / fmaxf(fabsf(key_float(kmn)), fabsf(key_float(kmx)))), lambda(tile_lambda(a, tile)) {}
+    __device__ __forceinline__ float4 operator()(int p, int q, c32 v, float h, [[maybe_unused]] float jraw = 0.0f, [[maybe_unused]] float jac0 = 0.0f) const
+    {
+#pragma clang fp contract(off)          // every instantiation rounds alike: frames are bit-identical whichever one a launch picks
+        const float s = ((p + q) & 1) ? -1.0f : 1.0f;
+        float w = 1.0f;
+        if constexpr (JAC) {        // (1 + l s dxDx)(1 + l s dzDz) - (l s dxDz)(l s dzDx), .cpp:422-426 (the two cross terms are one field)
+            const float cross = lambda * jraw;
+            w = jac0 - cross * cross;
+        }
+        return make_float4(s * lambda * v.x, h * inv_a, s * lambda * v.y, w);
+    }
+};
+
 // The body of k_xpass_b as a device function (k_frame runs it for the workgroups behind its z-pass ones).  bx: the workgroup's index among
 // the launch's x-axis workgroups; ONE: part of a one-launch frame -- all three roles (HEIGHT, NORMAL, DISP), every workgroup first waits until
 // the tile's z-pass workgroups of the same launch have counted themselves in (FrameArgs::zdone; they are dispatched first and wait for nobody),
@@ -1277,7 +1349,7 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     constexpr int LM = 1;                                 // last-stage lane layout (fft_engine.h): a wave = one map row, 1 KiB bursts
     TwiddleRegs<N, C, T, P, LM> twr;
     twr.load(a.tw, tid);
-    constexpr int NB = (HF::NU + C - 1) / C;              // normal workgroups
+    constexpr int NB = xpass_row_groups<N, C>();          // normal workgroups
     constexpr int HB = JAC ? NB : xpass_height_groups<N, C>();      // height workgroups
     static_assert(HF::NUP % (2 * C) == 0, "height row blocks");
     if constexpr (ONE) wait_counter_reached(a.zdone + tile, a.zdone_target, tid, a.poll_sleep, a.fault);      // the intermediates of THIS frame are all written (write-through)
@@ -1290,10 +1362,9 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         // height and cross derivative of rows u0 .. u0+C-1 out (both even: the mirrored rows hold the same values),
         // global min/max of the height.
         {
-            constexpr int NW = (T + 63) / 64;
-            float* red = reinterpret_cast<float*>(fbuf + fft_lds_elems<N, C>());
+            float* red = xpass_red<N, C>(smem);
             const int u0 = xcd_swizzle(bx, HB) * C;
-            const float2* __restrict__ z3 = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(a.z3) + (size_t)tile * HF::Z_GROUP * (Z16 ? 4 : 8));
+            const float2* __restrict__ z3 = z_base<Z16>(a.z3, (size_t)tile * HF::Z_GROUP);
             float* __restrict__ hraw = a.hraw + (size_t)tile * HF::HRAW_TILE;
             float* __restrict__ jraw = a.jraw + (size_t)tile * HF::HRAW_TILE;
             [[maybe_unused]] float ux = 1.0f, uy = 1.0f;
@@ -1311,18 +1382,7 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
                 at32(jraw, hraw_index(N, p, q)) = s * v.y * ig;
             };
             batch_fft<N, C, T, P>(fbuf, twr, tid, in, out);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                vmin = fminf(vmin, __shfl_xor(vmin, o));
-                vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-            }
-            if ((tid & 63) == 0) { red[tid >> 6] = vmin; red[NW + (tid >> 6)] = vmax; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int w = 1; w < NW; ++w) { vmin = fminf(vmin, red[w]); vmax = fmaxf(vmax, red[NW + w]); }
-                atomicMin(a.minmax + 2 * tile + 0, float_key(vmin));
-                atomicMax(a.minmax + 2 * tile + 1, float_key(vmax));
-            }
+            height_minmax_commit<T>(red, tid, vmin, vmax, a.minmax, tile);
         }
     }
     };
@@ -1331,11 +1391,9 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     // and the workgroup announces itself on a.hdone behind them (store_wt / wait_counter above).
     auto height_role = [&]() {
         const bool merged = a.xb_disp != 0;
-        constexpr int NW = (T + 63) / 64;
-        float* red = reinterpret_cast<float*>(fbuf + fft_lds_elems<N, C>());
+        float* red = xpass_red<N, C>(smem);
         const int u0 = xcd_swizzle(bx, HB) * 2 * C;
-        constexpr size_t ES = Z16 ? 4 : 8;
-        const float2* __restrict__ zh = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(a.zh) + (size_t)tile * HF::ZH_TILE * ES);
+        const float2* __restrict__ zh = z_base<Z16>(a.zh, (size_t)tile * HF::ZH_TILE);
         float* __restrict__ hraw = a.hraw + (size_t)tile * HF::HRAW_TILE;
         float vmin = 3.402823466e+38f, vmax = -3.402823466e+38f;
         [[maybe_unused]] const float uu = Z16 ? a.zscale[2 * tile].z : 1.0f;
@@ -1381,18 +1439,7 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         } else {
             batch_fft<N, C, T, P>(fbuf, twr, tid, in, out);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            vmin = fminf(vmin, __shfl_xor(vmin, o));
-            vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-        }
-        if ((tid & 63) == 0) { red[tid >> 6] = vmin; red[NW + (tid >> 6)] = vmax; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < NW; ++w) { vmin = fminf(vmin, red[w]); vmax = fmaxf(vmax, red[NW + w]); }
-            atomicMin(a.minmax + 2 * tile + 0, float_key(vmin));
-            atomicMax(a.minmax + 2 * tile + 1, float_key(vmax));
-        }
+        height_minmax_commit<T>(red, tid, vmin, vmax, a.minmax, tile);
         if (merged) {
             // every wave's write-through stores (and lane 0's two atomics) have been taken, then ONE lane counts the workgroup in
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1418,14 +1465,13 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     const int nid = bx - HB;
     const int u0 = (N >= 2048 ? (nid == 0 ? NB - 1 : xcd_swizzle(nid - 1, NB - 1)) : xcd_swizzle(nid, NB)) * C;
     start_ramp_wait(a.start_ramp, (unsigned)nid, (unsigned)NB);    // the NORMAL workgroups alone (one 2048^2 tile: ocean_launch.h)
-    constexpr size_t ESN = Z16 ? 4 : 8;
-    const float2* __restrict__ z1 = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(a.z) + ((size_t)tile * HF::Z_TILE + HF::Z_GROUP) * ESN);
-    const float2* __restrict__ z2 = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(z1) + HF::Z_GROUP * ESN);
+    const float2* __restrict__ z1 = pair_base<N, Z16>(a.z, tile, 1);
+    const float2* __restrict__ z2 = pair_base<N, Z16>(a.z, tile, 2);
     [[maybe_unused]] const float uk = Z16 ? a.zscale[2 * tile].w : 1.0f;
     float4* __restrict__ nrm = a.nrm + (size_t)tile * N * N;
     float4* __restrict__ nrm_host = a.nrm_host ? a.nrm_host + (size_t)tile * N * N : nullptr;
     [[maybe_unused]] float* __restrict__ jac0 = JAC ? a.jac0 + (size_t)tile * HF::HRAW_TILE : nullptr;
-    [[maybe_unused]] const float lambda = a.lambda ? a.lambda[tile] : a.lambda_all;
+    [[maybe_unused]] const float lambda = tile_lambda(a, tile);
     c32 held[LS::IT][LS::RL];
     auto texel = [&](int p, int q, c32 slopes, c32 derivs) -> float4 {
 #pragma clang fp contract(off)          // every instantiation of this kernel rounds alike: frames are bit-identical whichever one a launch picks
@@ -1443,12 +1489,7 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         if (q > N / 2) return;                                      // padding row
         const float4 o = texel(p, q, slopes, derivs);
         jac_factor(p, q, o);
-        OCEAN_STORE(nrm, q * N + p, o);
-        store_map_host(nrm_host, (unsigned)(q * N + p), o);
-        if (q != 0 && q != N / 2) {                                  // mirror: slopes odd, derivatives even
-            OCEAN_STORE(nrm, (N - q) * N + ((N - p) & (N - 1)), make_float4(-o.x, -o.y, o.z, o.w));
-            store_map_host(nrm_host, (unsigned)((N - q) * N + ((N - p) & (N - 1))), make_float4(-o.x, -o.y, o.z, o.w));
-        }
+        store_texel_and_mirror<N, NTS>(nrm, nrm_host, p, q, o, mirror_nrm{});
     };
     const c32 zero = make_float2(0.0f, 0.0f);
     // a full group's rows in the streamed form from 512^2 up: every output in registers first, then texel and whole-piece mirror, output by
@@ -1463,12 +1504,12 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
     };
     [[maybe_unused]] auto store_rows = [&]() {
         if constexpr (ROT) {
-            float4* hand = reinterpret_cast<float4*>(smem + mirror_handoff_offset<N, C, T>());
+            float4* hand = mirror_handoff<N, C, T>(smem);
             auto value = [&](int p, int q, int u, int i) { return texel(p, q, held[u][i], held2[u][i]); };
             publish_row_heads<N, LS, T>(hand, tid, u0, value);
             launder(held);
             launder(held2);
-            store_rows_whole<N, LS, T, NTS>(nrm, nrm_host, hand, tid, u0, value, jac_factor, [](float4 o) { return make_float4(-o.x, -o.y, o.z, o.w); });      // slopes odd, derivatives even
+            store_rows_whole<N, LS, T, NTS>(nrm, nrm_host, hand, tid, u0, value, jac_factor, mirror_nrm{});
         }
     };
     if constexpr (xpass_single_row_group<N, C>()) {
@@ -1562,7 +1603,7 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
         if constexpr (!JAC) {
             using LSD = LastStage<N, C, T, P, LM>;
             const int u0 = xcd_swizzle(bx - HB - NB, NB) * C;
-            const float2* __restrict__ z0 = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(a.z) + (size_t)tile * HF::Z_TILE * (Z16 ? 4 : 8));
+            const float2* __restrict__ z0 = pair_base<N, Z16>(a.z, tile, 0);
             [[maybe_unused]] const float uu = Z16 ? a.zscale[2 * tile].z : 1.0f;
             const float* __restrict__ hraw = a.hraw + (size_t)tile * HF::HRAW_TILE;
             float4* __restrict__ disp = a.disp + (size_t)tile * N * N;
@@ -1580,23 +1621,12 @@ __device__ __forceinline__ void xpass_b_body(const FrameArgs& a, unsigned char* 
             }
             wait_counter(a.hdone + tile, (unsigned)HB, tid, a.poll_sleep, a.fault);
             const unsigned kmn = load_wt(a.minmax + 2 * tile + 0), kmx = load_wt(a.minmax + 2 * tile + 1);      // final: every HEIGHT workgroup has counted itself in
-            const float mn = key_float(kmn), mx = key_float(kmx);
-            const float inv_a = 1.0f / fmaxf(fabsf(mn), fabsf(mx));
-            const float lambda = a.lambda ? a.lambda[tile] : a.lambda_all;
+            const DispTexel<false> texel(a, tile, kmn, kmx);
             for_each_output<LSD, T>(tid, [&](int p, int c, int u, int i) {
-#pragma clang fp contract(off)          // as in k_xpass_disp
                 const int q = u0 + c;
                 if (q > N / 2) return;
                 const float hv = load_wt(&at32(hraw, hraw_index(N, p, q)));
-                const float sg = ((p + q) & 1) ? -1.0f : 1.0f;
-                const c32 v = dheld[u][i];
-                const float4 o = make_float4(sg * lambda * v.x, hv * inv_a, sg * lambda * v.y, 1.0f);
-                store_map<NTS>(disp, (unsigned)(q * N + p), o);
-                store_map_host(disp_host, (unsigned)(q * N + p), o);
-                if (q != 0 && q != N / 2) {     // mirror: the displacements are odd, the height even
-                    store_map<NTS>(disp, (unsigned)((N - q) * N + ((N - p) & (N - 1))), make_float4(-o.x, o.y, -o.z, 1.0f));
-                    store_map_host(disp_host, (unsigned)((N - q) * N + ((N - p) & (N - 1))), make_float4(-o.x, o.y, -o.z, 1.0f));
-                }
+                store_texel_and_mirror<N, NTS>(disp, disp_host, p, q, texel(p, q, dheld[u][i], hv), mirror_disp{});
             });
         }
     };
@@ -1630,9 +1660,8 @@ template <int N, int C, int T, class PZ, class PX, bool NTS, bool Z16, bool FAST
 __global__ void __launch_bounds__(T) k_frame(const FrameArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using HF = Half<N>;
     constexpr int NZ = N / 2 + 1;
-    constexpr int NB = (HF::NU + C - 1) / C, HB = xpass_height_groups<N, C>();
+    constexpr unsigned XG = xpass_merged_groups<N, C>();      // the x-axis workgroups of a tile: the ones the records count
     const int bx = (int)blockIdx.x;
     if (bx < NZ) {
         zpass_body<N, T, PZ, false, Z16, 1, FAST, true>(a, smem, bx, NZ);
@@ -1641,7 +1670,7 @@ __global__ void __launch_bounds__(T) k_frame(const FrameArgs a)
         if (threadIdx.x == 0) __hip_atomic_fetch_add(a.zdone + blockIdx.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // ... then the workgroup counts itself in
         return;
     }
-    xpass_b_body<N, C, T, PX, NTS, Z16, false, true>(a, smem, bx - NZ, (unsigned)(HB + 2 * NB) * gridDim.y, (unsigned)blockIdx.y * (unsigned)(HB + 2 * NB) + (unsigned)(bx - NZ));
+    xpass_b_body<N, C, T, PX, NTS, Z16, false, true>(a, smem, bx - NZ, XG * gridDim.y, (unsigned)blockIdx.y * XG + (unsigned)(bx - NZ));
 }
 
 template <int N, int C, int T, class P = Plan<N>, bool NTS = false, bool Z16 = false, bool JAC = false>
@@ -1653,10 +1682,9 @@ __global__ void __launch_bounds__(T, (T == 512 ? 4 : 1)) k_xpass_disp(const Fram
     c32* fbuf = reinterpret_cast<c32*>(smem);
     const int tid = threadIdx.x;
     const int tile = blockIdx.y;
-    constexpr int NB = (HF::NU + C - 1) / C;
-    const int u0 = xcd_swizzle(blockIdx.x, NB) * C;
+    const int u0 = xcd_swizzle(blockIdx.x, xpass_row_groups<N, C>()) * C;
     start_ramp_wait(a.start_ramp, blockIdx.x, gridDim.x);   // (one 2048^2 tile: ocean_launch.h)
-    const float2* __restrict__ z0 = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(a.z) + (size_t)tile * HF::Z_TILE * (Z16 ? 4 : 8));
+    const float2* __restrict__ z0 = pair_base<N, Z16>(a.z, tile, 0);
     [[maybe_unused]] const float uu = Z16 ? a.zscale[2 * tile].z : 1.0f;
     const float* __restrict__ hraw = a.hraw + (size_t)tile * HF::HRAW_TILE;
     float4* __restrict__ disp = a.disp + (size_t)tile * N * N;
@@ -1687,32 +1715,16 @@ __global__ void __launch_bounds__(T, (T == 512 ? 4 : 1)) k_xpass_disp(const Fram
         }
         const unsigned kmn = a.minmax[2 * tile + 0], kmx = a.minmax[2 * tile + 1];      // final by now
         if (a.rec_mode == 1 && blockIdx.x == 0 && tid == 0) a.done_rec[tile] = make_uint4(kmn, kmx, a.frame_seq, 0u);
-        const float mn = key_float(kmn);
-        const float mx = key_float(kmx);
-        const float inv_a = 1.0f / fmaxf(fabsf(mn), fabsf(mx));
-        const float lambda = a.lambda ? a.lambda[tile] : a.lambda_all;
+        const DispTexel<JAC> disp_texel(a, tile, kmn, kmx);
         auto in = [&](int nf, int c, int, int) -> c32 { return load_pair_column<N, Z16>(z0, nf, u0 + c, -1.0f, uu); };
         auto texel = [&](int p, int q, c32 v, int u, int i) -> float4 {
-#pragma clang fp contract(off)          // as in k_xpass_b
-            const float s = ((p + q) & 1) ? -1.0f : 1.0f;
-            float w = 1.0f;
-            if constexpr (JAC) {        // (1 + l s dxDx)(1 + l s dzDz) - (l s dxDz)(l s dzDx), .cpp:422-426 (the two cross terms are one field)
-                const float cross = lambda * jv[u][i];
-                w = j0[u][i] - cross * cross;
-            }
-            return make_float4(s * lambda * v.x, hv[u][i] * inv_a, s * lambda * v.y, w);
+            if constexpr (JAC) return disp_texel(p, q, v, hv[u][i], jv[u][i], j0[u][i]);
+            else return disp_texel(p, q, v, hv[u][i]);
         };
         auto out = [&](int p, int c, c32 v, int u, int i) {
             const int q = u0 + c;
             if (q > N / 2) return;
-            const float4 o = texel(p, q, v, u, i);
-            const float w = o.w;
-            OCEAN_STORE(disp, q * N + p, o);
-            store_map_host(disp_host, (unsigned)(q * N + p), o);
-            if (q != 0 && q != N / 2) {     // mirror: the displacements are odd, height and Jacobian even
-                OCEAN_STORE(disp, (N - q) * N + ((N - p) & (N - 1)), make_float4(-o.x, o.y, -o.z, w));
-                store_map_host(disp_host, (unsigned)((N - q) * N + ((N - p) & (N - 1))), make_float4(-o.x, o.y, -o.z, w));
-            }
+            store_texel_and_mirror<N, NTS>(disp, disp_host, p, q, texel(p, q, v, u, i), mirror_disp{});
         };
         if constexpr (mirror_rotates<N, CC, T, P, LM, NTS>()) {
             // every output in registers first; then texel and whole-piece mirror, output by output (mirror_rotates)
@@ -1722,11 +1734,11 @@ __global__ void __launch_bounds__(T, (T == 512 ? 4 : 1)) k_xpass_disp(const Fram
                 for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) { hold(p, c, make_float2(0.0f, 0.0f), u, i); });
             else
                 batch_fft<N, CC, T, P>(fbuf, twr, tid, in, hold);
-            float4* hand = reinterpret_cast<float4*>(smem + mirror_handoff_offset<N, C, T>());
+            float4* hand = mirror_handoff<N, C, T>(smem);
             auto value = [&](int p, int q, int u, int i) { return texel(p, q, vh[u][i], u, i); };
             publish_row_heads<N, LS, T>(hand, tid, u0, value);
             launder(vh);
-            store_rows_whole<N, LS, T, NTS>(disp, disp_host, hand, tid, u0, value, [](int, int, float4) {}, [](float4 o) { return make_float4(-o.x, o.y, -o.z, o.w); });    // displacements odd, height and Jacobian even
+            store_rows_whole<N, LS, T, NTS>(disp, disp_host, hand, tid, u0, value, [](int, int, float4) {}, mirror_disp{});
         } else if (a.mode == 2)          // HEIGHT1: no horizontal displacement, no transform
             for_each_output<LS, T>(tid, [&](int p, int c, int u, int i) { out(p, c, make_float2(0.0f, 0.0f), u, i); });
         else

@@ -41,13 +41,10 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
     constexpr size_t lds_rows = zpass_lds_bytes<N, 1>();
     constexpr bool HAS2 = zpass_has_width2<N>();
     constexpr size_t lds_rows2 = zpass_lds_bytes<N, 2>();
-    // x passes: the FFT image (+ the HEIGHT role's per-wave min / max), and from 512^2 up the hand-off region of the mirrored rows behind both
-    constexpr size_t lds_hand = mirror_handoff_bytes<N, C, G::T_C, typename G::PC>();
-    constexpr size_t lds_m = lds_hand ? mirror_handoff_offset<N, C, G::T_C>() + lds_hand : sizeof(c32) * fft_lds_elems<N, C>();
-    constexpr size_t lds_b = lds_hand ? lds_m : sizeof(c32) * fft_lds_elems<N, C>() + sizeof(float) * 2 * ((G::T_C + 63) / 64);
+    constexpr size_t lds_m = xpass_disp_lds_bytes<N, C, G::T_C, typename G::PC>(), lds_b = xpass_b_lds_bytes<N, C, G::T_C, typename G::PC>();
     static_assert(lds_b <= 80 * 1024, "two x-pass workgroups per compute unit");
     static_assert(HF::NUP % (2 * C) == 0, "height row blocks");
-    constexpr unsigned hb_b = xpass_height_groups<N, C>(), nb = (HF::NU + C - 1) / C;
+    constexpr unsigned hb_b = xpass_height_groups<N, C>(), nb = xpass_row_groups<N, C>(), xg = xpass_merged_groups<N, C>();
     const bool fast = !a.h0h && a.omega_q;       // the usual form of the spectrum: fp32 h0, 16-bit dispersion
     const bool alone = p.alone;
     const unsigned cus = (unsigned)(c->cu_count > 0 ? c->cu_count : 0);
@@ -147,7 +144,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
     // hand-off's three dependent memory round trips cost more than the kernel boundary they replace: 512^2 16.6 -> 18.2 us); PIPELINED frames
     // of one tile up to 512^2, which are bound by the rate of launches, not by any kernel (512^2, depth 4: 13.2-14.9 -> 8.0 us per frame).
     bool merged_x = xmerge_pays<N>(alone) && tiles == 1 && a.mode != 3 && c->merged_x &&
-                    (hb_b + 2u * nb) <= c->tune.handoff_wg_per_cu * cus;
+                    xg <= c->tune.handoff_wg_per_cu * cus;
     // ONE launch for the whole frame (k_frame; round 5): pipelined frames of one tile up to 128^2 in the usual form (fp32 spectrum with 16-bit
     // dispersion, fp32 intermediates, both maps streamed, not the Jacobian mode) -- they are bound by the rate of launches.  Measured at depth 4,
     // us per frame, three launches / merged x pass / one launch: 64^2 11.5 / 7.6 / 3.9, 128^2 15.0 / 10.3 / 5.2 -- and 256^2 8.2-15.4 / 5.8 / 8.3,
@@ -158,7 +155,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
     // (like the merged x pass only where every workgroup of the grid has a slot at once -- one per compute unit, the regime the hand-off recipe is
     //  measured for: forward progress then never depends on the order in which workgroups are dispatched)
     bool one_launch = HAS_ONE && !alone && tiles == 1 && a.mode <= 2 && fast && p.nt_normal && p.nt_disp && !p.nt_inter && !p.half_inter && c->merged_x &&
-                      ((unsigned)(N / 2 + 1) + hb_b + 2u * nb) <= c->tune.handoff_wg_per_cu * cus;
+                      ((unsigned)(N / 2 + 1) + xg) <= c->tune.handoff_wg_per_cu * cus;
     // the DISP workgroups of a merged launch poll the HEIGHT count; beside other chains' launches a poll every ~3 us instead of back to back
     // takes the pollers off the memory system (512^2 depth 4: 7.66-7.97 -> 7.35-7.55 us per frame, 256^2 7.8-9.7 -> 7.2-7.3); a serial frame
     // (<= 128^2) keeps the tight poll -- there the wait IS the frame's latency -- and so does a one-launch frame
@@ -288,7 +285,7 @@ static hipError_t launch_frame(ocean_ctx* c, const FrameArgs& a, FrameLaunch& fl
             fa.xb_disp = 1; fa.rec_mode = rec_last; fa.start_ramp = 0;
             fa.zdone_target = (++c->zgen[fl.set]) * (unsigned)(N / 2 + 1);
             fa.poll_sleep = poll_sleep;
-            const dim3 grid((N / 2 + 1) + hb_b + 2 * nb, tiles), block(G::T_C);
+            const dim3 grid((N / 2 + 1) + xg, tiles), block(G::T_C);
             // (describe adds nothing: the one_launch rule above excludes half2 intermediates and the Jacobian mode)
             for (int k = 0; k < 3; ++k)
                 describe(k, grid.x, G::T_C, k == 0 ? 1u : (unsigned)C, lds_one, OCEAN_LAUNCH_ONE_LAUNCH | (k == 0 ? 0u : (OCEAN_LAUNCH_NT_MAPS | OCEAN_LAUNCH_MERGED_X)));
