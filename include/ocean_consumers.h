@@ -163,6 +163,90 @@ int ocean_sample_surface_lod_device(ocean_t* ctx, const ocean_surface* s, const 
 int ocean_displace_grid_lod(ocean_t* ctx, uint32_t first_tile, uint32_t count, uint32_t grid_size, float vertex_distance,
                             const float* uv_scales /* count */, float choppy, const ocean_lod* l);
 
+/* ---- surface bounds: min/max pyramids per tile, patch boxes, frustum classification ------------------------------------------------
+ * A renderer that draws the sea in patches decides every frame which patches to draw at all; for that it needs a box that is guaranteed
+ * to contain the DISPLACED patch.  The same box answers "can this patch have folds or foam at all?" (the lower bound of the Jacobian
+ * slot) and "can this body touch water?" before a buoyancy call.  Per-frame order: frame -> ocean_build_bounds_tiles ->
+ * ocean_patch_bounds(_device) -> draw.
+ * The pyramid   ocean_build_bounds_tiles builds, for each of the tiles first_tile .. first_tile+count-1 (count 1 .. tiles - first_tile),
+ *          two chains over the DISPLACEMENT map of the most recently enqueued frame, `lo` and `hi`, each in the packed layout of
+ *          ocean_build_mips (ocean_mip_texels(N) float4; level l = 1 .. log2 N, extent N >> l, starts at texel sum_{k=1}^{l-1} (N >> k)^2).
+ *          Node (y, x) of level l of `lo` holds, per channel (x, y, z, w), the fminf of the map's texels in rows y*2^l .. (y+1)*2^l - 1
+ *          and columns x*2^l .. (x+1)*2^l - 1; `hi` holds the fmaxf.  Level 0 is the map itself.  min and max are exact, so every node
+ *          has one value whatever the order of the reduction.  The maps are finite: what a NaN texel does to its nodes is unspecified,
+ *          and so is the sign of a zero node whose block holds zeros of both signs.
+ *          first_level: levels below it are NOT stored -- their place in the chain keeps its offset, its contents are unspecified (all
+ *          of it: a build may or may not write there).  0 means 1; 1 .. log2 N are valid, anything else is OCEAN_E_INVALID.  Culling
+ *          patches are rarely narrower than 8 texels and levels 1 and 2 are 94 % of a chain: this is what keeps the per-frame cost
+ *          near one read of the map.  The patch query never reads below the set's first_level.
+ *          Stream-ordered behind the most recently enqueued frame like every consumer (any pipeline depth, caller-bound or imported
+ *          output), at most two kernel launches whatever the count.  Two buffers owned by the context, [count][ocean_mip_texels(N)]
+ *          float4 each: they grow on demand (a growth that fails leaves no set), survive a new tile size and go with ocean_destroy.
+ *          The context remembers the frame, range and first_level the set was built from; a later call replaces the set.  A new
+ *          frame, ocean_prepare or ocean_set_tile_size makes it stale.  Memory: 2 * count * (N^2 - 1) / 3 * 16 bytes.
+ *          ocean_read_bounds_tile copies one tile's chains out (synchronises; either pointer may be NULL).  ocean_device_bounds_tiles
+ *          hands out the pointers (NULL while there is no set), the built range, the number of levels (log2 N) and first_level.
+ *          Errors: OCEAN_E_INVALID for a NULL context, count == 0, a range or tile outside the batch, a bad first_level;
+ *          OCEAN_E_NOT_READY without Prepare or frame, and for the read also without a set or for a tile outside the built range.
+ * The patch query   ocean_patch_bounds turns `count` rest-space rectangles (x0, z0, x1, z1 in mesh metres; the ends in either order)
+ *          into world-space boxes of the surface `s` describes (s->iterations and s->choppy are unused).  One thread per rectangle;
+ *          fp32 throughout, no contraction, in this order (tests/bounds.py repeats it step for step):
+ *   Axis range  for one axis with ends p0, p1 and cascade c:
+ *                 t(p) = ((p / vertex_distance + half) / grid_size) * uv_scales[c] * (float)N - 0.5f
+ *               exactly as ocean_query_surface forms u and its sampler the texel coordinate; pad = pad_texels;
+ *                 i0 = (int)floorf(fminf(t(p0), t(p1))) - pad,   i1 = (int)floorf(fmaxf(t(p0), t(p1))) + 1 + pad     (kept in 64 bits)
+ *               Every operation in t is monotone (non-decreasing or non-increasing in p, rounding included), so for any p between
+ *               the ends t(p) lies between t(p0) and t(p1), and the two texels floor(t(p)), floor(t(p)) + 1 the bilinear sampler
+ *               reads lie in i0 .. i1 -- for either sign of vertex_distance or uv_scales[c].  That is the reason for the rule.
+ *   Level       w = max(i1x - i0x, i1z - i0z) + 1 (64-bit: it cannot overflow).  If w >= N, or one of x0, z0, x1, z1 is not finite:
+ *               the single node of level log2 N.  Otherwise l = the smallest level with 2^l >= w, raised to the set's first_level.
+ *               A range of at most 2^l texels touches at most two nodes per axis, (i0 >> l) & m and (i1 >> l) & m with
+ *               m = (N >> l) - 1: the arithmetic shift of negative indices and the mask make this REPEAT.  lo_c / hi_c = the fminf /
+ *               fmaxf per channel over those <= 4 nodes of tile c's `lo` / `hi` chain.
+ *   Combine     as ocean_displace_grid_cascades, sums from 0.0f in cascade order:
+ *                 L.x += lo_c.x,  L.y += lo_c.y * A_c,  L.z += lo_c.z;   H likewise from hi_c;   Lw = fminf over c of lo_c.w from FLT_MAX
+ *               (A_c, the amplitude from the frame's height keys as in every consumer, is > 0: the product keeps the order.)
+ *   Output      out_lo = (fminf(x0, x1) + L.x,  0.0f + L.y,  fminf(z0, z1) + L.z,  Lw)
+ *               out_hi = (fmaxf(x0, x1) + H.x,  0.0f + H.y,  fmaxf(z0, z1) + H.z,  cls)
+ *   Class       cls = 1.0f when planes == 0.  Otherwise, for each plane (a, b, c, d) in order (inside is a*x + b*y + c*z + d >= 0):
+ *                 far  = ((a * (a >= 0 ? hi.x : lo.x) + b * (b >= 0 ? hi.y : lo.y)) + c * (c >= 0 ? hi.z : lo.z)) + d
+ *                 near = the same expression with the opposite corners
+ *               far < 0: cls = 0.0f (outside), and the later planes are not looked at;  near < 0 on any plane: cls = 1.0f (straddles);
+ *               otherwise cls = 2.0f (inside).
+ * Guarantee     For every rest point r inside the rectangle, the position the level-0 forward evaluation writes for r lies in
+ *          [out_lo, out_hi] on every axis, up to the rounding of the bilinear blend.  (The level-0 forward evaluation is
+ *          ocean_sample_surface_lod at footprint 0; it is the cascade vertex stage wherever that stage's u equals the query's.)  The
+ *          blend (c00*ia + c10*a)*ib + (c01*ia + c11*a)*b has 1 - a inexact by at most 2^-25 where a < 0.5, followed by five rounded
+ *          operations, so a sample exceeds the largest texel it reads by less than 2^-21 * max|texel|; the sums over the cascades and
+ *          the final additions add nothing, because rounding is monotone and both sides add the same terms in the same order.  The
+ *          Jacobian slot obeys w >= out_lo.w minus that slack.
+ *          Its limits: a caller whose u is formed differently sets pad_texels = 1 (the vertex stage divides integers, and
+ *          x / vertex_distance need not return the integer); one who samples at mip level L sets pad_texels = 2^(L+1).  The bound is
+ *          conservative, not tight: up to twice the range per axis goes into a box.
+ * Readiness: as for the LOD sampler -- OCEAN_E_NOT_READY unless a bounds set covers first_tile .. first_tile+cascades-1 and was built from
+ * the frame the call reads.  Other errors are those of ocean_query_surface (iterations are not looked at); additionally OCEAN_E_INVALID
+ * for a NULL q, planes > 6, one of the first `planes` planes that is not finite, pad_texels > 65536.  count == 0 returns OCEAN_OK before
+ * the pointers are looked at.  The host form stages [outputs | 16-byte inputs] in the context's buffer and returns when the results are
+ * there; the device form (rects 4-byte, outputs 16-byte aligned) is enqueued behind the most recent frame on its stream and returns at
+ * once.  Supported range as ocean_query_surface: the row of a rectangle outside it (NaN, +-inf, beyond 2^31 texels) is unspecified; the
+ * indices are masked, so it reads inside the chains and disturbs no other row.
+ * (An addition to ABI version 5: nothing of the existing entry points or structures changes.)                                        */
+int ocean_build_bounds_tiles(ocean_t* ctx, uint32_t first_tile, uint32_t count, uint32_t first_level /* 0 = 1 */);
+int ocean_read_bounds_tile(ocean_t* ctx, uint32_t tile, float* lo_chain, float* hi_chain);   /* either may be NULL */
+int ocean_device_bounds_tiles(ocean_t* ctx, void** d_lo, void** d_hi,
+                              uint32_t* first_tile, uint32_t* count, uint32_t* levels, uint32_t* first_level);
+typedef struct ocean_patch_query {
+    uint32_t pad_texels;        /* texels added on every side of each cascade's index range          default 0 */
+    uint32_t planes;            /* 0 .. 6 frustum planes; 0 = no classification                      default 0 */
+    float    plane[6][4];       /* (a, b, c, d): a point is inside where a*x + b*y + c*z + d >= 0; finite */
+} ocean_patch_query;
+void ocean_default_patch_query(ocean_patch_query* q);
+int ocean_patch_bounds(ocean_t* ctx, const ocean_surface* s, const ocean_patch_query* q,
+                       const float* rects /* 4 * count: x0, z0, x1, z1 in mesh metres, rest space */, uint32_t count,
+                       float* out_lo /* 4 * count */, float* out_hi /* 4 * count */);
+int ocean_patch_bounds_device(ocean_t* ctx, const ocean_surface* s, const ocean_patch_query* q,
+                              const void* d_rects, uint32_t count, void* d_out_lo, void* d_out_hi);
+
 /* ---- ray cast: where a ray first meets the water --------------------------------------------------------------------
  * Camera picking, projectiles and splashes, line of sight over the waves, a camera's near plane kept out of a crest, "is the
  * camera under water?".  The surface is exactly the one ocean_query_surface defines for the same ocean_surface (tiles,

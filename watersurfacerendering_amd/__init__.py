@@ -617,6 +617,72 @@ class OceanBatch:
         _abi.check(self._L.ocean_read_grid(self._h, pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)), "ocean_read_grid")
         return pos, nrm
 
+    # -- surface bounds (include/ocean_consumers.h: ocean_build_bounds_tiles, ocean_patch_bounds) ---------------------------------
+    def build_bounds_tiles(self, first_tile: int = 0, count: Optional[int] = None, first_level: int = 1):
+        """Min/max pyramids of the displacement maps of the tiles first_tile .. first_tile+count-1 (default: to the end of the batch)
+        behind the most recent frame (ocean_build_bounds_tiles): the set patch_bounds reads.  Levels below first_level are not stored.
+        Enqueued on the frame's stream; returns at once."""
+        n = self.tiles - int(first_tile) if count is None else int(count)
+        _abi.check(self._L.ocean_build_bounds_tiles(self._h, int(first_tile), n, int(first_level)), "ocean_build_bounds_tiles")
+
+    def read_bounds_tile(self, tile: int):
+        """One tile's chains of the set (ocean_read_bounds_tile; synchronises): a list of (lo, hi) per level l = 1 .. log2 N, each
+        (N >> l, N >> l, 4) float32.  Levels below the set's first_level hold nothing that is specified."""
+        texels = int(self._L.ocean_mip_texels(self.tile_size))
+        lo = np.empty((texels, 4), dtype=np.float32)
+        hi = np.empty_like(lo)
+        _abi.check(self._L.ocean_read_bounds_tile(self._h, int(tile), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)),
+                   "ocean_read_bounds_tile")
+        out, off, w = [], 0, self.tile_size // 2
+        while w >= 1:
+            out.append((lo[off:off + w * w].reshape(w, w, 4), hi[off:off + w * w].reshape(w, w, 4)))
+            off += w * w; w //= 2
+        return out
+
+    def device_bounds_tiles(self):
+        """(d_lo, d_hi, first_tile, count, levels, first_level) of the set (ocean_device_bounds_tiles); the pointers are None without one."""
+        lo, hi = C.c_void_p(), C.c_void_p()
+        first, count, levels, first_level = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _abi.check(self._L.ocean_device_bounds_tiles(self._h, C.byref(lo), C.byref(hi), C.byref(first), C.byref(count), C.byref(levels),
+                                                     C.byref(first_level)), "ocean_device_bounds_tiles")
+        return lo.value, hi.value, first.value, count.value, levels.value, first_level.value
+
+    @staticmethod
+    def _patch_query(planes, pad_texels) -> "_abi.PatchQuery":
+        q = _abi.PatchQuery()
+        pl = np.zeros((0, 4), np.float32) if planes is None else np.asarray(planes, dtype=np.float32).reshape(-1, 4)
+        if len(pl) > 6:
+            raise ValueError("planes: at most 6")
+        q.pad_texels, q.planes = int(pad_texels), len(pl)
+        for k, row in enumerate(pl):
+            for j in range(4):
+                q.plane[k][j] = float(row[j])
+        return q
+
+    def patch_bounds(self, rects, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                     vertex_distance: Optional[float] = None, planes=None, pad_texels: int = 0):
+        """World-space boxes of the displaced surface over the rest-space rectangles rects [count, 4] = (x0, z0, x1, z1 in mesh metres)
+        (ocean_patch_bounds; needs build_bounds_tiles behind the most recent frame).  Returns (lo, hi), each (count, 4) float32:
+        lo = (min x, min y, min z, lower bound of the Jacobian slot), hi = (max x, max y, max z, class).  planes [k, 4], k <= 6, rows
+        (a, b, c, d) with inside where a*x + b*y + c*z + d >= 0: class 0 outside, 1 straddles, 2 inside; without planes the class is 1."""
+        r = np.ascontiguousarray(rects, dtype=np.float32).reshape(-1, 4)
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, 0.0, 0)
+        q = self._patch_query(planes, pad_texels)
+        lo = np.empty((r.shape[0], 4), dtype=np.float32)
+        hi = np.empty_like(lo)
+        _abi.check(self._L.ocean_patch_bounds(self._h, C.byref(s), C.byref(q), r.ctypes.data_as(C.c_void_p), r.shape[0],
+                                              lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)), "ocean_patch_bounds")
+        return lo, hi
+
+    def patch_bounds_device(self, d_rects: int, count: int, d_lo: int, d_hi: int, first_tile: int = 0, uv_scales=(1.0,),
+                            grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, planes=None, pad_texels: int = 0):
+        """patch_bounds on device arrays of the context's device (ocean_patch_bounds_device): d_rects [count][4], d_lo / d_hi
+        [count][4] float32, 16-byte aligned.  Enqueued on the frame's stream (`stream`); returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, 0.0, 0)
+        q = self._patch_query(planes, pad_texels)
+        _abi.check(self._L.ocean_patch_bounds_device(self._h, C.byref(s), C.byref(q), C.c_void_p(d_rects), int(count), C.c_void_p(d_lo),
+                                                     C.c_void_p(d_hi)), "ocean_patch_bounds_device")
+
     def export_maps(self):
         """dma-buf of the current map set (ocean_export_maps): (fd, disp_offset, nrm_offset, bytes, map_set); close the fd yourself."""
         fd, ms = C.c_int(-1), C.c_int(0)

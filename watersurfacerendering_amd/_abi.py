@@ -46,6 +46,8 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_mip_texels", "ocean_build_mips", "ocean_read_mips", "ocean_device_mips",
     "ocean_build_mips_tiles", "ocean_read_mips_tile", "ocean_device_mips_tiles",
     "ocean_default_lod", "ocean_sample_surface_lod", "ocean_sample_surface_lod_device", "ocean_displace_grid_lod",
+    "ocean_build_bounds_tiles", "ocean_read_bounds_tile", "ocean_device_bounds_tiles",
+    "ocean_default_patch_query", "ocean_patch_bounds", "ocean_patch_bounds_device",
     "ocean_query_surface", "ocean_query_surface_device", "ocean_raycast_surface", "ocean_raycast_surface_device",
     "ocean_default_foam", "ocean_update_foam", "ocean_reset_foam", "ocean_read_foam", "ocean_device_foam", "ocean_query_foam", "ocean_query_foam_device",
     "ocean_default_buoyancy", "ocean_set_hull", "ocean_buoyancy_bodies", "ocean_buoyancy_bodies_device",
@@ -98,6 +100,11 @@ class Surface(C.Structure):
 class Lod(C.Structure):
     """struct ocean_lod (include/ocean_consumers.h): what scales the footprints of the LOD sampler and where its levels stop."""
     _fields_ = [("scale", C.c_float), ("max_level", C.c_uint32)]
+
+
+class PatchQuery(C.Structure):
+    """struct ocean_patch_query (include/ocean_consumers.h): the index padding of a patch query and the frustum planes it classifies against."""
+    _fields_ = [("pad_texels", C.c_uint32), ("planes", C.c_uint32), ("plane", (C.c_float * 4) * 6)]
 
 
 class Raycast(C.Structure):
@@ -267,6 +274,12 @@ def lib() -> C.CDLL:
         "ocean_sample_surface_lod": (i32, [P, C.POINTER(Surface), C.POINTER(Lod), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_sample_surface_lod_device": (i32, [P, C.POINTER(Surface), C.POINTER(Lod), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_displace_grid_lod": (i32, [P, u32, u32, u32, f32, FP, f32, C.POINTER(Lod)]),
+        "ocean_build_bounds_tiles": (i32, [P, u32, u32, u32]),
+        "ocean_read_bounds_tile": (i32, [P, u32, C.c_void_p, C.c_void_p]),
+        "ocean_device_bounds_tiles": (i32, [P, C.POINTER(P), C.POINTER(P), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
+        "ocean_default_patch_query": (None, [C.POINTER(PatchQuery)]),
+        "ocean_patch_bounds": (i32, [P, C.POINTER(Surface), C.POINTER(PatchQuery), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_patch_bounds_device": (i32, [P, C.POINTER(Surface), C.POINTER(PatchQuery), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_query_surface": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_query_surface_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_raycast_surface": (i32, [P, C.POINTER(Surface), C.POINTER(Raycast), C.c_void_p, u32, C.c_void_p, C.c_void_p]),

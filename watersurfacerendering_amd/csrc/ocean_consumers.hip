@@ -1,12 +1,13 @@
 // ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
-// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling) and the device memory those calls own.  Their kernels:
-// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling, surface bounds) and the device memory those calls own.  Their kernels:
+// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h, ocean_bounds_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
 #include <cmath>
 
 #include "ocean_ctx.h"
 #include "ocean_foam_kernels.h"     // (includes ocean_consumer_kernels.h)
 #include "ocean_buoyancy_kernels.h" // (includes ocean_velocity_kernels.h)
 #include "ocean_lod_kernels.h"
+#include "ocean_bounds_kernels.h"
 
 using namespace ocean;
 
@@ -87,10 +88,12 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     // their contents do not: they were made from maps that are gone
     c->mips_ready = false; c->grid_vertices = 0;
     c->lod_ready = false;           // (the set of ocean_build_mips_tiles likewise: its capacity is in texels, whatever the tile size)
+    c->bnd_ready = false;           // (... and that of ocean_build_bounds_tiles)
     if (!everything) return;
     free_and_null(c->grid_pos); free_and_null(c->grid_nrm); c->grid_capacity = 0;
     free_and_null(c->mips_disp); free_and_null(c->mips_nrm); c->mips_n = 0;
     free_and_null(c->lod_disp); free_and_null(c->lod_nrm); c->lod_capacity = 0;
+    free_and_null(c->bnd_lo); free_and_null(c->bnd_hi); c->bnd_capacity = 0;
     free_and_null(c->hull); c->hull_points = 0;
     if (c->consumer_ev) { (void)hipEventDestroy(c->consumer_ev); c->consumer_ev = nullptr; }
     c->consumer_pending = false;
@@ -541,6 +544,136 @@ int ocean_displace_grid_lod(ocean_t* c, uint32_t first_tile, uint32_t count, uin
     OCEAN_TRY(consumer_end(c, f.st));
     c->grid_vertices = verts;
     return OCEAN_OK;
+}
+
+}  // extern "C"
+
+// ---- surface bounds (include/ocean_consumers.h): min/max pyramids of a tile range, patch boxes and their frustum class -----------------------
+// ... of the patch query: the settings, the surface of the query (iterations and choppy do not matter here), then the set -- which must cover
+// the cascade set and have been built from exactly the frame the call reads.
+static int patch_args(ocean_ctx* c, const ocean_surface* s, const ocean_patch_query* q, LastFrame& f, PatchArgs& a)
+{
+    if (!c || !s || !q || q->planes > 6 || q->pad_texels > 65536) return OCEAN_E_INVALID;
+    for (uint32_t k = 0; k < q->planes; ++k)
+        for (int j = 0; j < 4; ++j)
+            if (!std::isfinite(q->plane[k][j])) return OCEAN_E_INVALID;
+    ocean_surface forward = *s;
+    forward.iterations = 0;
+    OCEAN_TRY(query_args(c, &forward, f, a.q));
+    if (!c->bnd_ready || c->bnd_frame != c->frame_serial || c->bnd_set != f.set) return OCEAN_E_NOT_READY;
+    if (s->first_tile < c->bnd_first || s->first_tile + s->cascades > c->bnd_first + c->bnd_count) return OCEAN_E_NOT_READY;
+    a.chain_texels = ocean_mip_texels(c->n);
+    a.lo = c->bnd_lo + (s->first_tile - c->bnd_first) * a.chain_texels;
+    a.hi = c->bnd_hi + (s->first_tile - c->bnd_first) * a.chain_texels;
+    a.top = (int)log2_of(c->n);
+    a.first_level = (int)c->bnd_first_level;
+    a.pad = (int)q->pad_texels;
+    a.planes = (int)q->planes;
+    for (int k = 0; k < 6; ++k)
+        for (int j = 0; j < 4; ++j) a.plane[k][j] = (uint32_t)k < q->planes ? q->plane[k][j] : 0.0f;
+    return OCEAN_OK;
+}
+
+static int launch_patch_bounds(PatchArgs& a, uint32_t count, const void* d_rects, void* d_out_lo, void* d_out_hi, hipStream_t st)
+{
+    a.rects = static_cast<const float*>(d_rects);
+    a.q.xz = nullptr;
+    a.q.out_pos = static_cast<float4*>(d_out_lo);
+    a.q.out_nrm = static_cast<float4*>(d_out_hi);
+    a.q.points = count;
+    hipLaunchKernelGGL(k_patch_bounds, dim3((a.q.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_build_bounds_tiles(ocean_t* c, uint32_t first_tile, uint32_t count, uint32_t first_level)
+{
+    if (!c || count == 0 || first_tile >= c->tiles || count > c->tiles - first_tile) return OCEAN_E_INVALID;
+    const uint32_t n = c->n, top = log2_of(n);
+    if (first_level == 0) first_level = 1;
+    if (first_level > top) return OCEAN_E_INVALID;
+    LastFrame f;
+    OCEAN_TRY(last_frame(c, first_tile, f));
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t chain = ocean_mip_texels(n), need = (size_t)count * chain;
+    if (need > c->bnd_capacity)
+        OCEAN_TRY(regrow(c, &c->bnd_lo, &c->bnd_hi, need * sizeof(float4), c->bnd_capacity, need, [c] { c->bnd_ready = false; }));
+    c->bnd_ready = false;           // until both launches are enqueued: a failure below leaves no set
+    BoundsTilesArgs m;
+    m.src[0] = m.src[1] = f.disp;
+    m.dst[0] = c->bnd_lo; m.dst[1] = c->bnd_hi;
+    m.src_stride = f.n2; m.chain_texels = chain; m.dst_offset = 0;
+    m.sw = (int)n; m.be = n < (uint32_t)MIP_BLOCK ? (int)n : MIP_BLOCK;
+    m.level = 1;
+    // (the second launch reads level 6 whatever first_level says: the first stores from min(first_level, 6) where there is a second)
+    m.store_from = (int)(n > (uint32_t)MIP_BLOCK && first_level > 6 ? 6 : first_level);
+    OCEAN_TRY(consumer_begin(c, f.st));
+    hipLaunchKernelGGL(k_bounds_tiles<false>, dim3((n / m.be) * (n / m.be), 1, count), dim3(256), 0, f.st, m);
+    if (n > (uint32_t)MIP_BLOCK) {  // levels 7 .. log2 N from level 6 of the two chains: one block per tile
+        size_t level6 = 0;
+        for (uint32_t k = 1; k < 6; ++k) level6 += (size_t)(n >> k) * (n >> k);
+        m.src[0] = c->bnd_lo + level6; m.src[1] = c->bnd_hi + level6;
+        m.src_stride = chain;
+        m.sw = m.be = (int)(n / MIP_BLOCK);
+        m.dst_offset = level6 + (size_t)m.sw * m.sw;
+        m.level = 7;
+        m.store_from = (int)first_level;
+        hipLaunchKernelGGL(k_bounds_tiles<true>, dim3(1, 1, count), dim3(256), 0, f.st, m);
+    }
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->bnd_first = first_tile; c->bnd_count = count; c->bnd_first_level = first_level;
+    c->bnd_frame = c->frame_serial; c->bnd_set = f.set;
+    c->bnd_ready = true;
+    return OCEAN_OK;
+}
+
+int ocean_read_bounds_tile(ocean_t* c, uint32_t tile, float* lo_chain, float* hi_chain)
+{
+    if (!c || tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!c->prepared || !c->have_frame || !c->bnd_ready || tile < c->bnd_first || tile - c->bnd_first >= c->bnd_count) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    const size_t chain = ocean_mip_texels(c->n), at = (tile - c->bnd_first) * chain;
+    if (lo_chain) HIP_TRY(hipMemcpy(lo_chain, c->bnd_lo + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
+    if (hi_chain) HIP_TRY(hipMemcpy(hi_chain, c->bnd_hi + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+int ocean_device_bounds_tiles(ocean_t* c, void** d_lo, void** d_hi, uint32_t* first_tile, uint32_t* count, uint32_t* levels, uint32_t* first_level)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (d_lo) *d_lo = c->bnd_ready ? c->bnd_lo : nullptr;
+    if (d_hi) *d_hi = c->bnd_ready ? c->bnd_hi : nullptr;
+    if (first_tile) *first_tile = c->bnd_ready ? c->bnd_first : 0;
+    if (count) *count = c->bnd_ready ? c->bnd_count : 0;
+    if (levels) *levels = c->bnd_ready ? log2_of(c->n) : 0;
+    if (first_level) *first_level = c->bnd_ready ? c->bnd_first_level : 0;
+    return OCEAN_OK;
+}
+
+void ocean_default_patch_query(ocean_patch_query* q)
+{
+    if (!q) return;
+    *q = ocean_patch_query{};
+}
+
+int ocean_patch_bounds(ocean_t* c, const ocean_surface* s, const ocean_patch_query* q, const float* rects, uint32_t count,
+                       float* out_lo, float* out_hi)
+{
+    LastFrame f;
+    PatchArgs a{};
+    return staged_call(c, patch_args(c, s, q, f, a), f, a, launch_patch_bounds, count, rects, 4, out_lo, out_hi, 2);
+}
+
+int ocean_patch_bounds_device(ocean_t* c, const ocean_surface* s, const ocean_patch_query* q, const void* d_rects, uint32_t count,
+                              void* d_out_lo, void* d_out_hi)
+{
+    LastFrame f;
+    PatchArgs a{};
+    return device_call(c, patch_args(c, s, q, f, a), f, a, launch_patch_bounds, count, d_rects, d_out_lo, d_out_hi, 2);
 }
 
 }  // extern "C"

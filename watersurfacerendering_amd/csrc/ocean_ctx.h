@@ -193,6 +193,16 @@ struct ocean_ctx {
     uint64_t lod_frame = 0;         // frame_serial and chain of the frame the set was built from
     int lod_set = 0;
     bool lod_ready = false;         // a set has been built since the last ocean_prepare / new tile size
+    // Min/max pyramids of the displacement maps of a tile range (ocean_build_bounds_tiles): [bnd_count][ocean_mip_texels(N)] per chain, the
+    // same packed layout; levels below bnd_first_level are not stored.  What ocean_patch_bounds reads: it remembers its frame as the set above.
+    float4* bnd_lo = nullptr;
+    float4* bnd_hi = nullptr;
+    size_t bnd_capacity = 0;        // texels per buffer
+    uint32_t bnd_first = 0, bnd_count = 0;  // the built range [bnd_first, bnd_first + bnd_count)
+    uint32_t bnd_first_level = 1;   // 1 .. log2 N
+    uint64_t bnd_frame = 0;         // frame_serial and chain of the frame the set was built from
+    int bnd_set = 0;
+    bool bnd_ready = false;         // a set has been built since the last ocean_prepare / new tile size
     uint64_t frame_serial = 0;      // successful frame enqueues of the context's whole life (never reset: no two frames share a number)
     std::vector<float> prep_length;        // [tiles] tile length the most recent ocean_prepare built the spectrum for
     std::vector<float> set_lambda[MAXD];    // [tiles] lambda and tile length of the frame that wrote each chain's maps
