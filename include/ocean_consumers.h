@@ -462,6 +462,69 @@ int ocean_buoyancy_bodies_flow(ocean_t* ctx, const ocean_surface* s, const ocean
 int ocean_buoyancy_bodies_flow_device(ocean_t* ctx, const ocean_surface* s, const ocean_buoyancy* b, const void* d_bodies, uint32_t count,
                                       void* d_out_force, void* d_out_torque);
 
+/* ---- spray emitters: the breaking vertices of a window, compacted into an ordered list ------------------------------------------------
+ * Every call above answers a question about points the caller already knows.  Spray, splash sounds, mist and whitecap decals ask the
+ * opposite one: WHERE on the surface is something happening in this frame?  ocean_emit_spray walks a window of the cascade vertex stage's
+ * grid on the device, keeps the vertices where the surface is breaking and writes them as a short list -- a few hundred rows instead of the
+ * (grid_size+1)^2 float4 a caller would otherwise copy out of ocean_displace_grid_cascades and test on the host.  Per-frame order:
+ * frame -> ocean_emit_spray(_device) -> the particle system.  The list is in ascending lattice index and the same bits on every run.
+ * A vertex is evaluated in this order; fp32 throughout, no contraction (tests/spray.py repeats it step for step):
+ *   Vertex      lattice index i = 0 .. nx*ny - 1 of the window is grid vertex xi = ix0 + i % nx, yi = iy0 + i / nx (int32; the sums wrap).
+ *               It is evaluated exactly as ocean_displace_grid_cascades evaluates vertex (xi, yi) for the tiles, grid_size, vertex_distance
+ *               and uv_scales of `s`:  px = (float)xi * vertex_distance,  u = (float)(xi + half) / (float)grid_size  (half = grid_size / 2,
+ *               an integer division; pz, v likewise from yi), every sample and sum in that call's order.  The window may lie outside
+ *               -half .. grid_size - half: REPEAT addressing makes the grid endless.  s->choppy and s->iterations are unused.
+ *   J           from the mode recorded for the frame that wrote the maps, as ocean_update_foam takes it; d, sl = the samples of cascade
+ *               c's displacement and normal map at (u, v) * uv_scales[c]:
+ *                 OCEAN_MODE_JACOBIAN frame:  J_c = d.w
+ *                 OCEAN_MODE_FULL7 frame:     J_c = (1.0f + lam_c * sl.z) * (1.0f + lam_c * sl.w), lam_c the lambda of tile c's frame
+ *                 CHOPPY5 / HEIGHT1 frame:    OCEAN_E_UNSUPPORTED
+ *               J = fminf over the cascades in cascade order, from FLT_MAX: the counterpart of w = min_c D_c.w and of the foam query's max.
+ *   V           the twin rule of ocean_query_velocity.  A set of which no tile has a twin: V = (0.0f, 0.0f, 0.0f), and min_rise is not
+ *               looked at.  A fully and consecutively twinned set: V = sum_c (d'.x, d'.y * A'_c, d'.z) from 0.0f in cascade order, d' the
+ *               sample of twin c's displacement map at the vertex's (u, v) * uv_scales[c].  A partly twinned set: OCEAN_E_INVALID.
+ *   Predicate   the vertex is listed where all of these hold:
+ *                 J < threshold                                        (a NaN never passes)
+ *                 with twins: V.y >= min_rise
+ *                 (h & ((1u << thin_log2) - 1u)) == 0,  h = hash(i + salt) in uint32 with wraparound,
+ *                 hash(x):  x ^= x >> 16;  x *= 0x7feb352du;  x ^= x >> 15;  x *= 0x846ca68bu;  x ^= x >> 16
+ *               thin_log2 = k keeps about one breaking vertex in 2^k; a salt that changes per frame moves the kept ones about.
+ *   Output      the passing vertices in ascending i; row r of the list is
+ *                 out_pos[r]   = (px + dx, 0.0f + dy, pz + dz, strength),  strength = fminf(fmaxf((threshold - J) * gain, 0.0f), 1.0f)
+ *                 out_vel[r]   = (V.x, V.y, V.z, J)
+ *                 out_index[r] = i
+ *               with (dx, dy, dz) the vertex stage's summed displacement.  Only rows 0 .. min(total, capacity) - 1 are written; later rows
+ *               keep what they held.  out_count = (total: every passing vertex, not capped;  rows written = min(total, capacity)) is
+ *               always written, also with capacity == 0 -- the way to size a list: the outputs are then not looked at and may be NULL.
+ * The compaction is three launches whatever the window (count per chunk of 1024 indices, a scan of the chunk counts by one workgroup,
+ * scatter); no launch waits on another workgroup and there are no atomics, which is what fixes the order and the bits.  Its scratch (132
+ * bytes per chunk) is owned by the context, grows on demand like the staging buffer and goes with ocean_destroy.
+ * Both calls read the most recently enqueued frame (caller-bound or imported output where it is) and are stream-ordered behind it like
+ * ocean_query_surface; the fault rule of ocean.h holds unchanged.  ocean_emit_spray: host arrays out_pos[4*capacity], out_vel[4*capacity],
+ * out_index[capacity], out_count[2], staged through the context's staging buffer; returns when the results are there.
+ * ocean_emit_spray_device: the same arrays in device memory of the context's device (out_pos / out_vel 16-byte, out_index / out_count
+ * 4-byte aligned); enqueued behind the most recent frame on its stream (ocean_stream), returns at once.
+ * Errors: those of ocean_query_surface for the surface (iterations are not looked at); additionally OCEAN_E_INVALID for a NULL p, nx or ny
+ * equal to 0 or nx * ny > 2^24, thin_log2 > 16, a threshold, gain or min_rise that is not finite, gain < 0, a NULL output with
+ * capacity > 0, a NULL out_count; OCEAN_E_NOT_READY without Prepare or frame.
+ * (An addition to ABI version 5: nothing of the existing entry points or structures changes.)                                        */
+typedef struct ocean_spray {
+    float    threshold;                /* a vertex breaks where J < threshold                            default 0.3 */
+    float    gain;                     /* strength = clamp((threshold - J) * gain, 0, 1); >= 0           default 2.5 */
+    float    min_rise;                 /* with twins: also requires V.y >= min_rise (m/s); finite        default 0   */
+    uint32_t thin_log2;                /* 0 .. 16: keep a breaking vertex only where the low thin_log2 bits of hash(i + salt) are 0 */
+    uint32_t salt;                     /* changes which vertices the thinning keeps; vary it per frame */
+    int32_t  ix0, iy0;                 /* window of grid vertices: xi = ix0 + i % nx, yi = iy0 + i / nx, i = 0 .. nx*ny - 1 */
+    uint32_t nx, ny;                   /* 1 <= nx, ny;  nx * ny <= 1 << 24 */
+} ocean_spray;
+
+void ocean_default_spray(ocean_spray* p);   /* the defaults above, no thinning; the grid is not known here: nx = ny = 0, the caller sets the window */
+int ocean_emit_spray(ocean_t* ctx, const ocean_surface* s, const ocean_spray* p, uint32_t capacity,
+                     float* out_pos /* 4 * capacity */, float* out_vel /* 4 * capacity */, uint32_t* out_index /* capacity */,
+                     uint32_t out_count[2] /* total breaking (not capped), rows written = min(total, capacity) */);
+int ocean_emit_spray_device(ocean_t* ctx, const ocean_surface* s, const ocean_spray* p, uint32_t capacity,
+                            void* d_out_pos, void* d_out_vel, void* d_out_index, void* d_out_count);
+
 /* ---- empirical wave spectra: JONSWAP / TMA, directional spreading, wavenumber bands ---------------------------------------
  * ocean_params describes the reference's Phillips sea, whose phillips_const is not a physical scale.  ocean_set_spectrum replaces a
  * tile's spectrum by an empirical one given as a sea state -- wind speed at 10 m (ocean_params.wind_speed, U), fetch F, water depth --

@@ -683,6 +683,52 @@ class OceanBatch:
         _abi.check(self._L.ocean_patch_bounds_device(self._h, C.byref(s), C.byref(q), C.c_void_p(d_rects), int(count), C.c_void_p(d_lo),
                                                      C.c_void_p(d_hi)), "ocean_patch_bounds_device")
 
+    # -- spray emitters (include/ocean_consumers.h: ocean_emit_spray) ----------------------------------------------------------------
+    def _spray(self, s, window, params) -> "_abi.Spray":
+        p = _abi.Spray()
+        self._L.ocean_default_spray(C.byref(p))
+        half = s.grid_size // 2
+        p.ix0, p.iy0, p.nx, p.ny = (-half, -half, s.grid_size + 1, s.grid_size + 1) if window is None else (int(x) for x in window)
+        for k, v in params.items():
+            if k not in ("threshold", "gain", "min_rise", "thin_log2", "salt"):
+                raise TypeError(f"emit_spray: unknown parameter {k}")
+            setattr(p, k, v)
+        return p
+
+    def emit_spray(self, capacity: int, window=None, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                   vertex_distance: Optional[float] = None, out=None, **params):
+        """The breaking vertices of a window of the cascade vertex stage's grid on the most recent frame (ocean_emit_spray), in ascending
+        lattice index.  window = (ix0, iy0, nx, ny) in grid vertices, default the whole grid (-half, -half, grid_size + 1, grid_size + 1);
+        params: threshold, gain, min_rise, thin_log2, salt of ocean_spray.  Returns (pos, vel, index, total): the rows that were written,
+        min(total, capacity) of them -- pos (n, 4) = (x, y, z, strength), vel (n, 4) = (V.x, V.y, V.z, J), index (n,) uint32 -- and the
+        number of breaking vertices in the window, not capped: capacity = 0 only counts.  out = (pos, vel, index) arrays of `capacity`
+        rows (float32, float32, uint32; C-contiguous) are written in place -- rows past the written ones keep what they held -- and the
+        results are views of them."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, 0.0, 0)
+        p = self._spray(s, window, params)
+        capacity = int(capacity)
+        if out is None:
+            out = (np.empty((capacity, 4), np.float32), np.empty((capacity, 4), np.float32), np.empty(capacity, np.uint32))
+        pos, vel, index = out
+        for a, dt, shape in ((pos, np.float32, (capacity, 4)), (vel, np.float32, (capacity, 4)), (index, np.uint32, (capacity,))):
+            if a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError("emit_spray: out = (pos, vel, index) of capacity rows: float32 [capacity, 4] twice, uint32 [capacity]")
+        count = (C.c_uint32 * 2)()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if capacity else None
+        _abi.check(self._L.ocean_emit_spray(self._h, C.byref(s), C.byref(p), capacity, ptr(pos), ptr(vel), ptr(index), count), "ocean_emit_spray")
+        n = int(count[1])
+        return pos[:n], vel[:n], index[:n], int(count[0])
+
+    def emit_spray_device(self, capacity: int, d_pos: int, d_vel: int, d_index: int, d_count: int, window=None, first_tile: int = 0,
+                          uv_scales=(1.0,), grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, **params):
+        """emit_spray on device arrays of the context's device (ocean_emit_spray_device): d_pos / d_vel [capacity][4] float32 (16-byte
+        aligned), d_index [capacity] uint32, d_count [2] uint32 = (total, rows written).  Enqueued on the frame's stream (`stream`);
+        returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, 0.0, 0)
+        p = self._spray(s, window, params)
+        _abi.check(self._L.ocean_emit_spray_device(self._h, C.byref(s), C.byref(p), int(capacity), C.c_void_p(d_pos), C.c_void_p(d_vel),
+                                                   C.c_void_p(d_index), C.c_void_p(d_count)), "ocean_emit_spray_device")
+
     def export_maps(self):
         """dma-buf of the current map set (ocean_export_maps): (fd, disp_offset, nrm_offset, bytes, map_set); close the fd yourself."""
         fd, ms = C.c_int(-1), C.c_int(0)

@@ -53,6 +53,7 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_default_buoyancy", "ocean_set_hull", "ocean_buoyancy_bodies", "ocean_buoyancy_bodies_device",
     "ocean_set_velocity_twin", "ocean_velocity_twin", "ocean_query_velocity", "ocean_query_velocity_device",
     "ocean_buoyancy_bodies_flow", "ocean_buoyancy_bodies_flow_device",
+    "ocean_default_spray", "ocean_emit_spray", "ocean_emit_spray_device",
     "ocean_default_spectrum", "ocean_set_spectrum", "ocean_get_spectrum", "ocean_spectrum_moments",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
@@ -126,6 +127,12 @@ class Body(C.Structure):
 class Buoyancy(C.Structure):
     """struct ocean_buoyancy (include/ocean_consumers.h): water density, gravity and the linear drag per submerged volume."""
     _fields_ = [("density", C.c_float), ("gravity", C.c_float), ("drag", C.c_float)]
+
+
+class Spray(C.Structure):
+    """struct ocean_spray (include/ocean_consumers.h): where a vertex counts as breaking, the thinning and the window of grid vertices."""
+    _fields_ = [("threshold", C.c_float), ("gain", C.c_float), ("min_rise", C.c_float), ("thin_log2", C.c_uint32), ("salt", C.c_uint32),
+                ("ix0", C.c_int32), ("iy0", C.c_int32), ("nx", C.c_uint32), ("ny", C.c_uint32)]
 
 
 class Spectrum(C.Structure):
@@ -301,6 +308,9 @@ def lib() -> C.CDLL:
         "ocean_query_velocity_device": (i32, [P, C.POINTER(Surface), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_buoyancy_bodies_flow": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_buoyancy_bodies_flow_device": (i32, [P, C.POINTER(Surface), C.POINTER(Buoyancy), C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_default_spray": (None, [C.POINTER(Spray)]),
+        "ocean_emit_spray": (i32, [P, C.POINTER(Surface), C.POINTER(Spray), u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ocean_emit_spray_device": (i32, [P, C.POINTER(Surface), C.POINTER(Spray), u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ocean_default_spectrum": (None, [C.POINTER(Spectrum)]),
         "ocean_set_spectrum": (i32, [P, u32, C.POINTER(Spectrum)]),
         "ocean_get_spectrum": (i32, [P, u32, C.POINTER(Spectrum)]),

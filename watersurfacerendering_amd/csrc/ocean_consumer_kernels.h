@@ -205,10 +205,12 @@ struct SurfaceEval {
     float jx, jz;                      // sum_c gain_c * (nrm_c.z, nrm_c.w)
 };
 
-__device__ __forceinline__ SurfaceEval eval_surface(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float rx, float rz)
+// The evaluation at a given (u, v): every cascade's two samples, summed as the cascade vertex stage sums them.  each(c, d, sl) is shown the
+// samples of cascade c before they are added -- for a caller that needs more of them than the sums (the spray emitters' per-cascade Jacobian).
+template <class Each>
+__device__ __forceinline__ SurfaceEval eval_surface_uv(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float u, float v, Each each)
 {
 #pragma clang fp contract(off)
-    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
     SurfaceEval e{0.0f, 0.0f, 0.0f, 3.402823466e+38f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) {
@@ -216,12 +218,21 @@ __device__ __forceinline__ SurfaceEval eval_surface(const QueryArgs& a, const fl
         const float us = u * a.uv_scale[c], vs = v * a.uv_scale[c];
         const float4 d = sample_linear_repeat(a.disp + (size_t)c * a.tile_texels, a.n, us, vs);
         const float4 sl = sample_linear_repeat(a.nrm + (size_t)c * a.tile_texels, a.n, us, vs);
+        each(c, d, sl);
         e.dx = e.dx + d.x; e.dy = e.dy + d.y * amp[c]; e.dz = e.dz + d.z;
         e.w = fminf(e.w, d.w);
         e.sx = e.sx + sl.x; e.sz = e.sz + sl.y; e.ddx = e.ddx + sl.z; e.ddz = e.ddz + sl.w;
         e.jx = e.jx + sl.z * a.gain[c]; e.jz = e.jz + sl.w * a.gain[c];
     }
     return e;
+}
+
+// ... at rest point (rx, rz): the (u, v) the query forms from it.
+__device__ __forceinline__ SurfaceEval eval_surface(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float rx, float rz)
+{
+#pragma clang fp contract(off)
+    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
+    return eval_surface_uv(a, amp, u, v, [](int, const float4&, const float4&) {});
 }
 
 __device__ __forceinline__ float clamp_jacobian(float j)

@@ -1,6 +1,6 @@
 // ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
-// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling, surface bounds) and the device memory those calls own.  Their kernels:
-// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h, ocean_bounds_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling, surface bounds, spray emitters) and the device memory those calls own.  Their kernels:
+// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h, ocean_bounds_kernels.h, ocean_spray_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
 #include <cmath>
 
 #include "ocean_ctx.h"
@@ -8,6 +8,7 @@
 #include "ocean_buoyancy_kernels.h" // (includes ocean_velocity_kernels.h)
 #include "ocean_lod_kernels.h"
 #include "ocean_bounds_kernels.h"
+#include "ocean_spray_kernels.h"
 
 using namespace ocean;
 
@@ -95,6 +96,7 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     free_and_null(c->lod_disp); free_and_null(c->lod_nrm); c->lod_capacity = 0;
     free_and_null(c->bnd_lo); free_and_null(c->bnd_hi); c->bnd_capacity = 0;
     free_and_null(c->hull); c->hull_points = 0;
+    free_and_null(c->spray_scratch); c->spray_chunks = 0;
     if (c->consumer_ev) { (void)hipEventDestroy(c->consumer_ev); c->consumer_ev = nullptr; }
     c->consumer_pending = false;
 }
@@ -730,6 +732,113 @@ int ocean_query_velocity_device(ocean_t* c, const ocean_surface* s, const void* 
     LastFrame f;
     VelocityArgs a{};
     return device_call(c, velocity_args(c, s, f, a), f, a, launch_velocity, points, d_xz, d_out_pos, d_out_vel, 2);
+}
+
+}  // extern "C"
+
+// ---- spray emitters (include/ocean_consumers.h): the breaking vertices of a window, compacted in lattice order --------------------------------
+// Checks and launch arguments: the settings, the surface of the query (iterations and choppy do not matter here), the Jacobian the frame's
+// mode left in the maps (as ocean_update_foam takes it), then the twins -- none at all is a set without velocities, some is an error.
+static int spray_args(ocean_ctx* c, const ocean_surface* s, const ocean_spray* p, uint32_t capacity, LastFrame& f, SprayArgs& a)
+{
+    if (!c || !s || !p || p->nx == 0 || p->ny == 0 || (uint64_t)p->nx * p->ny > ((uint64_t)1 << 24) || p->thin_log2 > 16 ||
+        !std::isfinite(p->threshold) || !std::isfinite(p->gain) || !std::isfinite(p->min_rise) || p->gain < 0.0f)
+        return OCEAN_E_INVALID;
+    ocean_surface forward = *s;
+    forward.iterations = 0;
+    OCEAN_TRY(query_args(c, &forward, f, a.q));
+    const int mode = c->set_mode[f.set];            // of the frame that wrote these maps, not of the next one
+    if (mode != OCEAN_MODE_FULL7 && mode != OCEAN_MODE_JACOBIAN) return OCEAN_E_UNSUPPORTED;
+    a.from_slot = mode == OCEAN_MODE_JACOBIAN;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) a.lam[i] = i < s->cascades ? c->set_lambda[f.set][s->first_tile + i] : 0.0f;
+    const int twins = twin_maps(c, s, f, a.tw);
+    if (twins != OCEAN_OK && twins != OCEAN_E_NOT_READY) return twins;
+    a.twinned = twins == OCEAN_OK;
+    a.threshold = p->threshold; a.gain = p->gain; a.min_rise = p->min_rise;
+    a.thin_mask = (1u << p->thin_log2) - 1u; a.salt = p->salt;
+    a.ix0 = p->ix0; a.iy0 = p->iy0; a.half = (int)(s->grid_size / 2);
+    a.nx = p->nx; a.points = p->nx * p->ny;
+    a.capacity = capacity;
+    a.chunks = (a.points + SPRAY_CHUNK - 1u) / SPRAY_CHUNK;
+    return OCEAN_OK;
+}
+
+// The three launches behind one another on the frame's stream, on the scratch of the compaction (ocean_ctx::spray_scratch; grown below).
+static int launch_spray(ocean_ctx* c, SprayArgs& a, void* d_out_pos, void* d_out_vel, void* d_out_index, void* d_out_count, hipStream_t st)
+{
+    a.masks = static_cast<unsigned long long*>(c->spray_scratch);
+    a.counts = reinterpret_cast<unsigned*>(a.masks + (size_t)c->spray_chunks * SPRAY_MASKS);
+    a.out_pos = static_cast<float4*>(d_out_pos);
+    a.out_vel = static_cast<float4*>(d_out_vel);
+    a.out_index = static_cast<unsigned*>(d_out_index);
+    a.out_count = static_cast<unsigned*>(d_out_count);
+    hipLaunchKernelGGL(k_spray_count, dim3(a.chunks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_spray_scan, dim3(1), dim3(256), 0, st, a);
+    if (a.capacity) hipLaunchKernelGGL(k_spray_scatter, dim3(a.chunks), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+static int grow_spray_scratch(ocean_ctx* c, const SprayArgs& a)
+{
+    if (a.chunks <= c->spray_chunks) return OCEAN_OK;
+    const size_t bytes = (size_t)a.chunks * (SPRAY_MASKS * sizeof(unsigned long long) + sizeof(unsigned));
+    return regrow(c, &c->spray_scratch, (void**)nullptr, bytes, c->spray_chunks, a.chunks, [] {});
+}
+
+extern "C" {
+
+void ocean_default_spray(ocean_spray* p)
+{
+    if (!p) return;
+    *p = ocean_spray{};
+    p->threshold = 0.3f;
+    p->gain = 2.5f;
+}
+
+int ocean_emit_spray(ocean_t* c, const ocean_surface* s, const ocean_spray* p, uint32_t capacity,
+                     float* out_pos, float* out_vel, uint32_t* out_index, uint32_t out_count[2])
+{
+    LastFrame f;
+    SprayArgs a{};
+    OCEAN_TRY(spray_args(c, s, p, capacity, f, a));
+    if (!out_count || (capacity && (!out_pos || !out_vel || !out_index))) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(grow_spray_scratch(c, a));
+    // [positions | velocities | indices | the two counts]: the float4 arrays first, so that every array is aligned
+    const size_t rows16 = (size_t)capacity * sizeof(float4), rows4 = (size_t)capacity * sizeof(uint32_t);
+    const size_t bytes = 2 * rows16 + rows4 + 2 * sizeof(uint32_t);
+    if (bytes > c->staging_bytes) OCEAN_TRY(regrow(c, &c->staging, (void**)nullptr, bytes, c->staging_bytes, bytes, [] {}));
+    char* d_pos = static_cast<char*>(c->staging);
+    char* d_vel = d_pos + rows16;
+    char* d_index = d_vel + rows16;
+    char* d_count = d_index + rows4;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    OCEAN_TRY(launch_spray(c, a, d_pos, d_vel, d_index, d_count, f.st));
+    HIP_TRY(hipMemcpyAsync(out_count, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, f.st));
+    OCEAN_TRY(consumer_end(c, f.st));
+    HIP_TRY(hipStreamSynchronize(f.st));
+    const size_t written = out_count[1];            // only the rows that were written travel: the caller's later rows keep what they held
+    if (written == 0) return OCEAN_OK;
+    HIP_TRY(hipMemcpyAsync(out_pos, d_pos, written * sizeof(float4), hipMemcpyDeviceToHost, f.st));
+    HIP_TRY(hipMemcpyAsync(out_vel, d_vel, written * sizeof(float4), hipMemcpyDeviceToHost, f.st));
+    HIP_TRY(hipMemcpyAsync(out_index, d_index, written * sizeof(uint32_t), hipMemcpyDeviceToHost, f.st));
+    HIP_TRY(hipStreamSynchronize(f.st));
+    return OCEAN_OK;
+}
+
+int ocean_emit_spray_device(ocean_t* c, const ocean_surface* s, const ocean_spray* p, uint32_t capacity,
+                            void* d_out_pos, void* d_out_vel, void* d_out_index, void* d_out_count)
+{
+    LastFrame f;
+    SprayArgs a{};
+    OCEAN_TRY(spray_args(c, s, p, capacity, f, a));
+    if (!d_out_count || (capacity && (!d_out_pos || !d_out_vel || !d_out_index))) return OCEAN_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(grow_spray_scratch(c, a));
+    OCEAN_TRY(consumer_begin(c, f.st));
+    OCEAN_TRY(launch_spray(c, a, d_out_pos, d_out_vel, d_out_index, d_out_count, f.st));
+    return consumer_end(c, f.st);
 }
 
 }  // extern "C"

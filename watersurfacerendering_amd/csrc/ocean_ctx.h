@@ -224,6 +224,11 @@ struct ocean_ctx {
     // sums instead of reading stray memory.  Independent of the maps: kept across ocean_prepare / ocean_set_tile_size, freed by ocean_destroy.
     float4* hull = nullptr;
     uint32_t hull_points = 0;
+    // Scratch of ocean_emit_spray's compaction: [spray_chunks][16] ballot masks (64 bits each), then [spray_chunks] chunk counts / offsets.
+    // Grown to the largest window seen; the consumer calls are ordered among themselves, so one call's three launches have it to themselves.
+    // Independent of the maps: kept across ocean_prepare / ocean_set_tile_size, freed by ocean_destroy.
+    void* spray_scratch = nullptr;
+    uint32_t spray_chunks = 0;
     unsigned long long* stamps = nullptr;   // diagnostic builds only
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain

@@ -22,13 +22,12 @@ __device__ __forceinline__ void twin_amplitudes(const QueryArgs& a, const TwinMa
         tamp[c] = c < a.count ? fmaxf(fabsf(key_float(tw.minmax[2 * c + 0])), fabsf(key_float(tw.minmax[2 * c + 1]))) : 0.0f;
 }
 
-// V at rest point r: the twins' displacement maps at the uv eval_surface samples the sources at, summed in cascade order from 0.0f.
-// One bilinear float4 gather per cascade, outside the Newton loop.
-__device__ __forceinline__ void water_velocity(const QueryArgs& a, const TwinMaps& tw, const float (&tamp)[OCEAN_MAX_CASCADES], float rx, float rz,
-                                               float& vx, float& vy, float& vz)
+// V at a given (u, v): the twins' displacement maps at the uv the sources are sampled at, summed in cascade order from 0.0f.
+// One bilinear float4 gather per cascade.
+__device__ __forceinline__ void water_velocity_uv(const QueryArgs& a, const TwinMaps& tw, const float (&tamp)[OCEAN_MAX_CASCADES], float u, float v,
+                                                  float& vx, float& vy, float& vz)
 {
 #pragma clang fp contract(off)
-    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
     vx = 0.0f; vy = 0.0f; vz = 0.0f;
 #pragma unroll
     for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) {
@@ -36,6 +35,15 @@ __device__ __forceinline__ void water_velocity(const QueryArgs& a, const TwinMap
         const float4 d = sample_linear_repeat(tw.disp + (size_t)c * a.tile_texels, a.n, u * a.uv_scale[c], v * a.uv_scale[c]);
         vx = vx + d.x; vy = vy + d.y * tamp[c]; vz = vz + d.z;
     }
+}
+
+// ... at rest point r: the uv eval_surface samples the sources at, outside the Newton loop.
+__device__ __forceinline__ void water_velocity(const QueryArgs& a, const TwinMaps& tw, const float (&tamp)[OCEAN_MAX_CASCADES], float rx, float rz,
+                                               float& vx, float& vy, float& vz)
+{
+#pragma clang fp contract(off)
+    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
+    water_velocity_uv(a, tw, tamp, u, v, vx, vy, vz);
 }
 
 // Velocity query: one thread per point; the K + 1 evaluations of the surface query, then one more gather per cascade from the twins.
