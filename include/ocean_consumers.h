@@ -590,6 +590,100 @@ int ocean_set_spectrum(ocean_t* ctx, uint32_t tile /* or OCEAN_ALL_TILES */, con
 int ocean_get_spectrum(const ocean_t* ctx, uint32_t tile, ocean_spectrum* s);
 int ocean_spectrum_moments(ocean_t* ctx, uint32_t tile, double out[3]);
 
+/* ---- Gerstner proxy: a tile's strongest waves as rows, evaluated analytically at any point and any time --------------------------------
+ * The reference's to-do "Gerstner waves model" (README.md:37-44).  Every call above reads the maps of the most recently enqueued frame; none
+ * can answer "how high is the water at (x, z) two seconds from now?" (a helmsman, a projectile's landing point, a netcode rollback) without
+ * spending a frame, none evaluates the surface between texels other than bilinearly, and a process without the maps (a game server) cannot
+ * reproduce the sea at all.  The sea is a finite sum of standing trochoidal waves, one per spectrum bin, and for a wind sea a few hundred
+ * bins carry almost all of the variance: a tile's WAVE SET is the list of its K strongest bins, and these calls evaluate such a list -- the
+ * surface the cascade vertex stage draws, truncated to K waves per tile.  Per-Prepare order: ocean_prepare -> ocean_extract_waves per tile.
+ * Per frame: nothing; ocean_eval_waves / ocean_query_waves at any t, with or without frames.
+ * The row      ocean_wave, 12 words: one bin of the tile's N x N lattice.  A CPU-only process evaluates rows like this, for a tile of N
+ *          texels whose position in tile lengths is (X, Z) (X = x / L for a tile that starts at the origin; the calls below form it from
+ *          the mesh, see there):
+ *            c(t)  = 2 (re cos(omega t) - im sin(omega t))          (the bin's h~, exactly real: the mirror bin is folded in)
+ *            theta = 2 pi (jx X + jz Z)                              (the reference's (-1)^(m+n) is the N/2 in jx = q - N/2)
+ *            h    += c cos theta
+ *            Dx   += ux c sin theta        Dz   += uz c sin theta    (the displacement map's x, z before lambda)
+ *            sx   -= kx c sin theta        sz   -= kz c sin theta    (the normal map's x, y)
+ *            dxDx += kx ux c cos theta     dzDz += kz uz c cos theta (the normal map's z, w)
+ *          At X = n / N, Z = m / N the sum over ALL bins is texel (m, n) of the frame's maps (with disp.y * A the height).
+ * Extraction   ocean_extract_waves reads the tile's prepared fp32 spectrum and omega -- what ocean_read_spectrum returns; never the
+ *          half-precision copy the frames may read -- and lists the strongest bins: power p = re*re + im*im in fp32 without contraction;
+ *          candidates are the bins with p > 0 (a NaN never passes); rank by p descending, ties by bin ascending; rows 0 .. count-1 are the
+ *          list in rank order, count = min(max_waves, candidates), 1 <= max_waves <= 4096.  Every field is a function of the spectrum
+ *          alone, the same bits on every run (tests/waves.py restates them).  out_energy[0] = the sum over the rows, in list order, of
+ *          (double)re*(double)re + (double)im*(double)im: divide by ocean_spectrum_moments' out[0] for the captured share of the variance.
+ *          The list stays on the device as the tile's wave set (one per tile; a later call replaces it; no candidate: no set) together
+ *          with N and the tile length it was made for.  The call synchronises, as ocean_spectrum_moments does.  On the device: a radix
+ *          select over (power bits, ~bin) keys -- at most eight 8-bit histogram passes, four or fewer unless a tie straddles rank K --,
+ *          one pass that collects the survivors, the host orders those <= 4096.  A twin tile lists its derivative spectrum: its set is
+ *          the velocity proxy (tile length, lambda and time offset are its source's, as for its frames).
+ *          ocean_prepare and ocean_set_tile_size drop every set: the sea they belonged to is gone.
+ * Hand-made    ocean_set_waves uploads rows as given (artist-made swell, crafted sets): every float finite and jx, jz in -N/2 .. N/2-1,
+ *          checked on the host, otherwise OCEAN_E_INVALID and the old set stays; bin and reserved are not looked at; count == 0 drops the
+ *          set.  ocean_get_waves copies the set out (synchronises; rows may be NULL to ask for the count).
+ * Evaluation   ocean_eval_waves is the FORWARD evaluation at rest points (x, z) (s->iterations unused); it needs Prepare and a set for each
+ *          of the tiles first_tile .. first_tile+cascades-1, no frame and no map.  fp32; lam_c is the tile's lambda at the time of the call,
+ *          N and L_c the ones the set recorded.  Per rest point and cascade c:
+ *            tt = t + the tile's time offset (ocean_set_time_offsets), one addition as in the frames
+ *            per wave: wt = omega * tt (ONE fp32 multiply), c = 2 (re cos wt - im sin wt) with the frames' sine and cosine
+ *            (u, v) as ocean_query_surface forms them;  tx = (u * uv_scales[c]) * (float)N - 0.5f (the sampler's texel coordinate);
+ *            X = tx * (1.0f / N);  fX = X - floorf(X);  Z, fZ likewise from v      -- at a texel centre exactly the texel's lattice point
+ *            per wave: a = (float)jx * fX,  b = (float)jz * fZ,  ph = (a - floorf(a)) + (b - floorf(b)) turns,  theta = 2 pi ph
+ *            the seven sums above
+ *          Over the cascades, in cascade order:
+ *            P = (x + sum_c lam_c Dx_c,  sum_c h_c,  z + sum_c lam_c Dz_c),   S = sum_c (sx, sz, dxDx, dzDz),
+ *            J = min_c (1 + lam_c dxDx_c)(1 + lam_c dzDz_c), from FLT_MAX
+ *            out_pos = (P, J),   out_nrm = (normalize(-S.x / (1 + choppy S.z), 1, -S.y / (1 + choppy S.w)), 0): the vertex stage's formula
+ *          Precision: sine and cosine cannot be restated bit for bit and the ORDER OF THE SUM is not part of the contract, so the results
+ *          are held to a derived bound, not to bits: each of the seven sums of a cascade is within
+ *            2^-21 * sum_j a_j g_j (|jx_j| + |jz_j| + 4 + K/8),   a_j = 2 (|re_j| + |im_j|),  g_j = 1, |ux|, |uz|, |kx|, |kz|, |kx ux|, |kz uz|
+ *          of the exact sum of the rows with c_j rounded as above (tests/waves.py has the derivation and what the outputs add to it).
+ *          Same rows and arguments give the same bits on every run and in both forms.
+ * The inverse  ocean_query_waves is ocean_query_surface's diagonal Newton iteration on that evaluation: r_0 = q; for k < K (= s->iterations,
+ *          0 means 8):  e = P(r_k).xz - q,
+ *            Jx = 1 + sum_c lam_c dxDx_c * s_c * L_c / (grid_size * vertex_distance),   Jz likewise from dzDz
+ *          (dxDx is per ocean metre of tile c and one mesh metre is s_c * L_c / (grid_size * vertex_distance) of them -- the map query's
+ *          factor; it is 1 where the mesh spans one tile), |J| clamped to >= 0.1 as there, r_{k+1} = r_k - (e.x / Jx, e.z / Jz);
+ *            out_pos = (P(r_K), J),   out_nrm = (n(r_K), |P(r_K).xz - q|)
+ *          With t this is the call that answers "where will the water be".
+ * Host / device forms as ocean_sample_surface_lod / _device: the host form stages [outputs | 8-byte inputs] in the context's buffer and
+ * returns when the results are there; the device form (xz 8-byte, outputs 16-byte aligned) is enqueued on the consumers' stream
+ * (ocean_stream), ordered among the other consumer calls, and returns at once.
+ * How many waves: K is chosen from the captured share out_energy / m0 -- 0.9 of the variance is 0.95 of the rms height.  Memory:
+ * tiles * 4096 * 48 bytes of sets, 1.5 MB for the evaluation's table (8 cascades * 4096 waves * 48 bytes) and 50 KB of selection scratch, allocated on first use, freed by ocean_destroy.
+ * Not covered: merging a bin with its point mirror into one row (on the Nyquist row and column the two are not mirror images off the
+ * lattice, so rows stay single bins and a caller picks K accordingly); waves off the tile's lattice; a vertex-stage or buoyancy form of the
+ * proxy; any accuracy claim for contexts that run the fp16 spectrum (the sets are made from the fp32 one).
+ * Errors: OCEAN_E_INVALID for a NULL context, count pointer, surface; a tile outside the batch; max_waves 0 or above 4096; a count above
+ * 4096 or a row that fails the check above; the invalid ocean_surface cases of ocean_query_surface; a t that is not finite; a NULL array
+ * with points > 0.  OCEAN_E_NOT_READY before Prepare, and for ocean_get_waves and the evaluations without a set (for every tile of the
+ * surface).  points == 0 returns OCEAN_OK before the pointers are looked at.
+ * (An addition to ABI version 5: nothing of the existing entry points or structures changes.)                                            */
+typedef struct ocean_wave {            /* 12 words, 48 bytes */
+    int32_t  jx, jz;                   /* lattice indices: bin column q = jx + N/2, row p = jz + N/2; -N/2 .. N/2-1 */
+    float    kx, kz;                   /* the tile's fp32 wavenumbers k1d[q], k1d[p] */
+    float    ux, uz;                   /* kx * r, kz * r, r = 1.0f / sqrtf(kx*kx + kz*kz); (0, 0) where sqrtf(...) <= 1e-5f */
+    float    re, im;                   /* h0 of the bin */
+    float    omega;                    /* the bin's quantised fp32 omega */
+    uint32_t bin;                      /* p * N + q in the layout ocean_read_spectrum returns */
+    float    reserved[2];              /* 0 */
+} ocean_wave;
+
+int ocean_extract_waves(ocean_t* ctx, uint32_t tile, uint32_t max_waves, ocean_wave* out /* max_waves rows; may be NULL */,
+                        uint32_t* out_count, double* out_energy /* may be NULL */);
+int ocean_set_waves(ocean_t* ctx, uint32_t tile, const ocean_wave* rows, uint32_t count);
+int ocean_get_waves(ocean_t* ctx, uint32_t tile, ocean_wave* rows /* may be NULL */, uint32_t* count);
+int ocean_eval_waves(ocean_t* ctx, const ocean_surface* s, float t, const float* xz /* 2 * points */, uint32_t points,
+                     float* out_pos /* 4 * points */, float* out_nrm /* 4 * points */);
+int ocean_eval_waves_device(ocean_t* ctx, const ocean_surface* s, float t, const void* d_xz, uint32_t points,
+                            void* d_out_pos, void* d_out_nrm);
+int ocean_query_waves(ocean_t* ctx, const ocean_surface* s, float t, const float* xz /* 2 * points */, uint32_t points,
+                      float* out_pos /* 4 * points */, float* out_nrm /* 4 * points */);
+int ocean_query_waves_device(ocean_t* ctx, const ocean_surface* s, float t, const void* d_xz, uint32_t points,
+                             void* d_out_pos, void* d_out_nrm);
+
 #ifdef __cplusplus
 }
 #endif

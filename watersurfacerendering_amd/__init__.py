@@ -28,11 +28,15 @@ import numpy as np
 from . import _abi
 from ._abi import OceanError, Params, build  # noqa: F401
 
-__all__ = ["WSTessendorf", "OceanBatch", "OceanError", "build", "host_register", "host_unregister", "comm_unique_id", "BODY_DTYPE"]
+__all__ = ["WSTessendorf", "OceanBatch", "OceanError", "build", "host_register", "host_unregister", "comm_unique_id", "BODY_DTYPE", "WAVE_DTYPE"]
 
 #: struct ocean_body (include/ocean_consumers.h) as a numpy record: what OceanBatch.buoyancy takes
 BODY_DTYPE = np.dtype([("pos", np.float32, 3), ("quat", np.float32, 4), ("vel", np.float32, 3), ("omega", np.float32, 3),
                        ("first_point", np.uint32), ("points", np.uint32), ("reserved", np.uint32)])
+
+#: struct ocean_wave (include/ocean_consumers.h) as a numpy record: what OceanBatch.extract_waves returns and set_waves takes
+WAVE_DTYPE = np.dtype([("jx", np.int32), ("jz", np.int32), ("kx", np.float32), ("kz", np.float32), ("ux", np.float32), ("uz", np.float32),
+                       ("re", np.float32), ("im", np.float32), ("omega", np.float32), ("bin", np.uint32), ("reserved", np.float32, 2)])
 
 
 def _is_pow2(n: int) -> bool:
@@ -728,6 +732,70 @@ class OceanBatch:
         p = self._spray(s, window, params)
         _abi.check(self._L.ocean_emit_spray_device(self._h, C.byref(s), C.byref(p), int(capacity), C.c_void_p(d_pos), C.c_void_p(d_vel),
                                                    C.c_void_p(d_index), C.c_void_p(d_count)), "ocean_emit_spray_device")
+
+    # -- Gerstner proxy (include/ocean_consumers.h: ocean_extract_waves, ocean_eval_waves, ocean_query_waves) -------------------------
+    def extract_waves(self, max_waves: int, tile: int = 0):
+        """The tile's strongest spectrum bins as its wave set (ocean_extract_waves): (rows, energy) -- rows a WAVE_DTYPE record array in
+        rank order (power descending, ties by bin), count = min(max_waves, bins with power > 0) of them; energy = sum |h0|^2 over the
+        rows as float64 (divide by spectrum_moments()[0] for the captured share of the variance).  The set stays on the device for
+        eval_waves / query_waves.  Synchronises."""
+        rows = np.zeros(max(int(max_waves), 1), dtype=WAVE_DTYPE)
+        count, energy = C.c_uint32(0), C.c_double(0.0)
+        _abi.check(self._L.ocean_extract_waves(self._h, int(tile), int(max_waves), rows.ctypes.data_as(C.c_void_p), C.byref(count),
+                                               C.byref(energy)), "ocean_extract_waves")
+        return rows[:count.value], float(energy.value)
+
+    def set_waves(self, rows, tile: int = 0):
+        """Upload a hand-made wave set (ocean_set_waves): rows a WAVE_DTYPE record array of at most 4096 rows; none drops the set."""
+        rows = np.ascontiguousarray(rows, dtype=WAVE_DTYPE).reshape(-1)
+        _abi.check(self._L.ocean_set_waves(self._h, int(tile), rows.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows)), "ocean_set_waves")
+
+    def get_waves(self, tile: int = 0) -> np.ndarray:
+        """The tile's wave set as a WAVE_DTYPE record array (ocean_get_waves).  Synchronises."""
+        count = C.c_uint32(0)
+        _abi.check(self._L.ocean_get_waves(self._h, int(tile), None, C.byref(count)), "ocean_get_waves")
+        rows = np.zeros(count.value, dtype=WAVE_DTYPE)
+        _abi.check(self._L.ocean_get_waves(self._h, int(tile), rows.ctypes.data_as(C.c_void_p), C.byref(count)), "ocean_get_waves")
+        return rows
+
+    def _waves_call(self, fn, name, xz, t, s):
+        q = np.ascontiguousarray(xz, dtype=np.float32).reshape(-1, 2)
+        pos = np.empty((q.shape[0], 4), dtype=np.float32)
+        nrm = np.empty_like(pos)
+        _abi.check(fn(self._h, C.byref(s), float(t), q.ctypes.data_as(C.c_void_p), q.shape[0], pos.ctypes.data_as(C.c_void_p),
+                      nrm.ctypes.data_as(C.c_void_p)), name)
+        return pos, nrm
+
+    def eval_waves(self, xz, t: float, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                   vertex_distance: Optional[float] = None, choppy: float = -1.0):
+        """Forward evaluation of the wave sets of tiles first_tile .. first_tile+len(uv_scales)-1 at rest points xz [points, 2] and time t
+        (ocean_eval_waves): no frame is read.  Returns (pos, nrm), each (points, 4) float32: pos = (x, height, z, smallest diagonal
+        Jacobian), nrm = (unit normal, 0).  Defaults as displace_grid."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, 0)
+        return self._waves_call(self._L.ocean_eval_waves, "ocean_eval_waves", xz, t, s)
+
+    def query_waves(self, xz, t: float, first_tile: int = 0, uv_scales=(1.0,), grid_size: Optional[int] = None,
+                    vertex_distance: Optional[float] = None, choppy: float = -1.0, iterations: int = 8):
+        """The water of the wave sets above world points xz [points, 2] at time t (ocean_query_waves): query_surface's Newton iteration
+        on the analytic evaluation.  Returns (pos, nrm) as query_surface: nrm[:, 3] is the residual |P.xz - xz| in metres."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        return self._waves_call(self._L.ocean_query_waves, "ocean_query_waves", xz, t, s)
+
+    def eval_waves_device(self, d_xz: int, points: int, d_pos: int, d_nrm: int, t: float, first_tile: int = 0, uv_scales=(1.0,),
+                          grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0):
+        """eval_waves on device arrays of the context's device (ocean_eval_waves_device): d_xz [points][2], d_pos / d_nrm [points][4]
+        float32.  Enqueued on the consumers' stream (`stream`); returns at once."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, 0)
+        _abi.check(self._L.ocean_eval_waves_device(self._h, C.byref(s), float(t), C.c_void_p(d_xz), int(points), C.c_void_p(d_pos),
+                                                   C.c_void_p(d_nrm)), "ocean_eval_waves_device")
+
+    def query_waves_device(self, d_xz: int, points: int, d_pos: int, d_nrm: int, t: float, first_tile: int = 0, uv_scales=(1.0,),
+                           grid_size: Optional[int] = None, vertex_distance: Optional[float] = None, choppy: float = -1.0,
+                           iterations: int = 8):
+        """query_waves on device arrays (ocean_query_waves_device), as eval_waves_device."""
+        s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
+        _abi.check(self._L.ocean_query_waves_device(self._h, C.byref(s), float(t), C.c_void_p(d_xz), int(points), C.c_void_p(d_pos),
+                                                    C.c_void_p(d_nrm)), "ocean_query_waves_device")
 
     def export_maps(self):
         """dma-buf of the current map set (ocean_export_maps): (fd, disp_offset, nrm_offset, bytes, map_set); close the fd yourself."""

@@ -55,6 +55,7 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_buoyancy_bodies_flow", "ocean_buoyancy_bodies_flow_device",
     "ocean_default_spray", "ocean_emit_spray", "ocean_emit_spray_device",
     "ocean_default_spectrum", "ocean_set_spectrum", "ocean_get_spectrum", "ocean_spectrum_moments",
+    "ocean_extract_waves", "ocean_set_waves", "ocean_get_waves", "ocean_eval_waves", "ocean_eval_waves_device", "ocean_query_waves", "ocean_query_waves_device",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
     "ocean_read_spectrum", "ocean_read_xi",
@@ -140,6 +141,12 @@ class Spectrum(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("spreading", C.c_uint32), ("fetch", C.c_float), ("gamma", C.c_float), ("depth", C.c_float),
                 ("spread_s", C.c_float), ("swell", C.c_float), ("alpha", C.c_float), ("peak_omega", C.c_float),
                 ("k_min", C.c_float), ("k_max", C.c_float), ("scale", C.c_float)]
+
+
+class Wave(C.Structure):
+    """struct ocean_wave (include/ocean_consumers.h): one spectrum bin of a tile's wave set; 12 words."""
+    _fields_ = [("jx", C.c_int32), ("jz", C.c_int32), ("kx", C.c_float), ("kz", C.c_float), ("ux", C.c_float), ("uz", C.c_float),
+                ("re", C.c_float), ("im", C.c_float), ("omega", C.c_float), ("bin", C.c_uint32), ("reserved", C.c_float * 2)]
 
 
 last_build = ""      # what the most recent build() did, for the caller to log
@@ -315,6 +322,13 @@ def lib() -> C.CDLL:
         "ocean_set_spectrum": (i32, [P, u32, C.POINTER(Spectrum)]),
         "ocean_get_spectrum": (i32, [P, u32, C.POINTER(Spectrum)]),
         "ocean_spectrum_moments": (i32, [P, u32, C.POINTER(C.c_double)]),
+        "ocean_extract_waves": (i32, [P, u32, u32, C.c_void_p, C.POINTER(u32), C.POINTER(C.c_double)]),
+        "ocean_set_waves": (i32, [P, u32, C.c_void_p, u32]),
+        "ocean_get_waves": (i32, [P, u32, C.c_void_p, C.POINTER(u32)]),
+        "ocean_eval_waves": (i32, [P, C.POINTER(Surface), f32, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_eval_waves_device": (i32, [P, C.POINTER(Surface), f32, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_query_waves": (i32, [P, C.POINTER(Surface), f32, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_query_waves_device": (i32, [P, C.POINTER(Surface), f32, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_set_mode": (i32, [P, i32]),
         "ocean_set_dispersion": (i32, [P, i32, f32]),
         "ocean_set_spectrum_precision": (i32, [P, i32]),

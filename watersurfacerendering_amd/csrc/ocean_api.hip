@@ -697,6 +697,7 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
     c->have_frame = false;
     c->lod_ready = false;                       // (the mip set of ocean_build_mips_tiles belongs to a frame of the old spectrum)
     c->bnd_ready = false;                       // (the bounds set of ocean_build_bounds_tiles likewise)
+    c->wave_count.assign(t, 0u);                // (the wave sets were lists of the old spectrum's bins)
     if (c->fault) *c->fault = 0u;
     return placement_search(c);
 }

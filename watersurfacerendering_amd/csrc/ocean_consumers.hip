@@ -1,6 +1,7 @@
 // ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
-// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling, surface bounds, spray emitters) and the device memory those calls own.  Their kernels:
-// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h, ocean_bounds_kernels.h, ocean_spray_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+// cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling, surface bounds, spray emitters) and the device memory those calls own -- and the Gerstner proxy, which reads the prepared spectrum instead.  Their kernels:
+// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h, ocean_bounds_kernels.h, ocean_spray_kernels.h, ocean_waves_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+#include <algorithm>
 #include <cmath>
 
 #include "ocean_ctx.h"
@@ -9,6 +10,7 @@
 #include "ocean_lod_kernels.h"
 #include "ocean_bounds_kernels.h"
 #include "ocean_spray_kernels.h"
+#include "ocean_waves_kernels.h"
 
 using namespace ocean;
 
@@ -90,6 +92,7 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     c->mips_ready = false; c->grid_vertices = 0;
     c->lod_ready = false;           // (the set of ocean_build_mips_tiles likewise: its capacity is in texels, whatever the tile size)
     c->bnd_ready = false;           // (... and that of ocean_build_bounds_tiles)
+    std::fill(c->wave_count.begin(), c->wave_count.end(), 0u);      // (the wave sets name bins of a lattice that is gone; their buffers stay)
     if (!everything) return;
     free_and_null(c->grid_pos); free_and_null(c->grid_nrm); c->grid_capacity = 0;
     free_and_null(c->mips_disp); free_and_null(c->mips_nrm); c->mips_n = 0;
@@ -97,6 +100,7 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     free_and_null(c->bnd_lo); free_and_null(c->bnd_hi); c->bnd_capacity = 0;
     free_and_null(c->hull); c->hull_points = 0;
     free_and_null(c->spray_scratch); c->spray_chunks = 0;
+    free_and_null(c->waves); free_and_null(c->wave_anim); free_and_null(c->wave_scratch);
     if (c->consumer_ev) { (void)hipEventDestroy(c->consumer_ev); c->consumer_ev = nullptr; }
     c->consumer_pending = false;
 }
@@ -1104,6 +1108,208 @@ int ocean_buoyancy_bodies_flow_device(ocean_t* c, const ocean_surface* s, const 
                                       void* d_out_force, void* d_out_torque)
 {
     return buoyancy_device<true>(c, s, b, d_bodies, count, d_out_force, d_out_torque);
+}
+
+}  // extern "C"
+
+// ---- Gerstner proxy (include/ocean_consumers.h): a tile's strongest waves as rows, their analytic evaluation and its Newton inverse ---------
+// Scratch of the selection, in 32-bit words: the digit counts and the candidates' count, the select counter, then the survivors as
+// (power bits, bin) pairs and, behind them, the sorted bins k_wave_rows reads.
+constexpr size_t WAVE_HIST = 0, WAVE_COUNTER = 257, WAVE_LIST = 260, WAVE_BINS = WAVE_LIST + 2 * WAVES_MAX, WAVE_SCRATCH_WORDS = WAVE_BINS + WAVES_MAX;
+
+static int alloc_waves(ocean_ctx* c)
+{
+    if (!c->waves) HIP_TRY(hipMalloc(&c->waves, (size_t)c->tiles * WAVES_MAX * sizeof(ocean_wave)));
+    if (!c->wave_anim) HIP_TRY(hipMalloc(&c->wave_anim, (size_t)OCEAN_MAX_CASCADES * WAVES_MAX * WAVES_ANIM_VEC * sizeof(float4)));
+    if (!c->wave_scratch) HIP_TRY(hipMalloc(&c->wave_scratch, WAVE_SCRATCH_WORDS * sizeof(unsigned)));
+    if (c->wave_count.size() != c->tiles) c->wave_count.assign(c->tiles, 0u);
+    if (c->wave_length.size() != c->tiles) c->wave_length.assign(c->tiles, 0.0f);
+    return OCEAN_OK;
+}
+
+static bool wave_set_exists(const ocean_ctx* c, uint32_t tile) { return tile < c->wave_count.size() && c->wave_count[tile] != 0; }
+
+// Checks and launch arguments of the two evaluations: the surface as the map query checks it, a finite time, Prepare, a set for every cascade.
+static int wave_eval_args(ocean_ctx* c, const ocean_surface* s, float t, bool inverse, LastFrame& f, WaveEvalArgs& a)
+{
+    if (!c || !s || s->cascades == 0 || s->cascades > (uint32_t)OCEAN_MAX_CASCADES || s->first_tile >= c->tiles ||
+        s->cascades > c->tiles - s->first_tile || s->grid_size == 0 || s->iterations > 32 || !std::isfinite(t))
+        return OCEAN_E_INVALID;
+    if (!c->prepared) return OCEAN_E_NOT_READY;
+    for (uint32_t i = 0; i < s->cascades; ++i)
+        if (!wave_set_exists(c, s->first_tile + i)) return OCEAN_E_NOT_READY;
+    f = LastFrame{};
+    f.set = c->last_set;
+    f.st = stream_of(c, f.set);            // no frame is read: the consumers' stream only orders the call among the other consumer calls
+    a.set.rows = c->waves + (size_t)s->first_tile * WAVES_MAX;
+    a.set.anim = c->wave_anim;
+    a.cascades = (int)s->cascades;
+    a.iterations = inverse ? (s->iterations ? (int)s->iterations : 8) : 0;
+    a.fn = (float)c->n; a.inv_n = 1.0f / (float)c->n;
+    a.grid = (float)s->grid_size;
+    a.half = (float)(s->grid_size / 2);
+    a.vertex_distance = s->vertex_distance;
+    a.choppy = s->choppy;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) {
+        a.set.count[i] = 0; a.set.tt[i] = 0.0f;
+        a.uv_scale[i] = 0.0f; a.lam[i] = 0.0f; a.gain[i] = 0.0f;
+        if (i >= s->cascades) continue;
+        const uint32_t tile = s->first_tile + i, e = effective_tile(c, tile);
+        a.set.count[i] = c->wave_count[tile];
+        a.set.tt[i] = t + (c->use_toff ? c->toff_host[e] : 0.0f);       // as the frames: a.t + toff[tile], one fp32 addition
+        a.uv_scale[i] = s->uv_scales[i];
+        a.lam[i] = c->params[e].lambda;
+        a.gain[i] = a.lam[i] * (s->uv_scales[i] * c->wave_length[tile] / (a.grid * s->vertex_distance));
+    }
+    return OCEAN_OK;
+}
+
+template <bool INVERSE>
+static int launch_waves(WaveEvalArgs& a, uint32_t points, const void* d_xz, void* d_out_pos, void* d_out_nrm, hipStream_t st)
+{
+    a.xz = static_cast<const float2*>(d_xz);
+    a.out_pos = static_cast<float4*>(d_out_pos);
+    a.out_nrm = static_cast<float4*>(d_out_nrm);
+    a.points = points;
+    hipLaunchKernelGGL(k_waves_animate, dim3(WAVES_MAX / 256u, (unsigned)a.cascades), dim3(256), 0, st, a.set);
+    if (INVERSE) hipLaunchKernelGGL(k_waves_query, dim3((a.points + 255u) / 256u), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_waves_eval, dim3((a.points + 255u) / 256u), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+int ocean_extract_waves(ocean_t* c, uint32_t tile, uint32_t max_waves, ocean_wave* out, uint32_t* out_count, double* out_energy)
+{
+    if (!c || !out_count || tile >= c->tiles || max_waves == 0 || max_waves > WAVES_MAX) return OCEAN_E_INVALID;
+    if (!c->prepared) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    OCEAN_TRY(alloc_waves(c));
+    const unsigned n = c->n, log2n = log2_of(n);
+    const size_t n2 = (size_t)n * n;
+    const float2* h0 = c->h0 + tile * n2;
+    hipStream_t st = stream_of(c, 0);
+    const unsigned blocks = (unsigned)std::min<size_t>((n2 + 2047) / 2048, 2048);
+    unsigned* hist = c->wave_scratch + WAVE_HIST;
+    unsigned* counter = c->wave_scratch + WAVE_COUNTER;
+    // the K-th largest key, digit by digit from the top; `remaining` is its rank among the keys that share the digits found so far
+    unsigned long long threshold = 0;
+    uint32_t count = 0, remaining = 0;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        unsigned h[257];
+        HIP_TRY(hipMemsetAsync(hist, 0, 258 * sizeof(unsigned), st));
+        hipLaunchKernelGGL(k_wave_hist, dim3(blocks), dim3(256), 0, st, h0, n, log2n, threshold, shift, hist);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, hist, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (shift == 56) {
+            count = std::min<uint32_t>(max_waves, h[256]);
+            remaining = count;
+            if (count == 0) break;
+        }
+        unsigned digit = 255, above = 0;
+        while (above + h[digit] < remaining) { above += h[digit]; if (digit == 0) return OCEAN_E_HIP; --digit; }
+        remaining -= above;
+        threshold |= (unsigned long long)digit << shift;
+        if (h[digit] == remaining) break;           // the whole bucket is taken: the digits below do not matter
+        if (shift == 0) return OCEAN_E_HIP;         // (distinct keys: the last digit's bucket holds one key)
+    }
+    std::vector<ocean_wave> rows(count);
+    if (count) {
+        uint2* list = reinterpret_cast<uint2*>(c->wave_scratch + WAVE_LIST);
+        unsigned* bins = c->wave_scratch + WAVE_BINS;
+        unsigned taken = 0;
+        hipLaunchKernelGGL(k_wave_select, dim3(blocks), dim3(256), 0, st, h0, n, log2n, threshold, WAVES_MAX, counter, list);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&taken, counter, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (taken != count) return OCEAN_E_HIP;
+        std::vector<uint2> pairs(count);
+        HIP_TRY(hipMemcpy(pairs.data(), list, count * sizeof(uint2), hipMemcpyDeviceToHost));
+        std::sort(pairs.begin(), pairs.end(), [](const uint2& x, const uint2& y) { return x.x != y.x ? x.x > y.x : x.y < y.y; });   // power descending, bin ascending
+        std::vector<unsigned> order(count);
+        for (uint32_t j = 0; j < count; ++j) order[j] = pairs[j].y;
+        HIP_TRY(hipMemcpyAsync(bins, order.data(), count * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        ocean_wave* set = c->waves + (size_t)tile * WAVES_MAX;
+        c->wave_count[tile] = 0;                    // from here on the old rows are being overwritten: a failure below leaves no set, not a mixed one
+        hipLaunchKernelGGL(k_wave_rows, dim3((count + 255u) / 256u), dim3(256), 0, st, h0, c->omega + tile * n2, c->k1d + (size_t)tile * n, n,
+                           bins, count, set);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rows.data(), set, count * sizeof(ocean_wave), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    c->wave_count[tile] = count;                    // (no candidate: no set)
+    c->wave_length[tile] = c->prep_length[tile];
+    *out_count = count;
+    double energy = 0.0;
+    for (uint32_t j = 0; j < count; ++j) {
+        if (out) out[j] = rows[j];
+        energy += (double)rows[j].re * (double)rows[j].re + (double)rows[j].im * (double)rows[j].im;
+    }
+    if (out_energy) *out_energy = energy;
+    return OCEAN_OK;
+}
+
+int ocean_set_waves(ocean_t* c, uint32_t tile, const ocean_wave* rows, uint32_t count)
+{
+    if (!c || tile >= c->tiles || count > WAVES_MAX || (count && !rows)) return OCEAN_E_INVALID;
+    if (!c->prepared) return OCEAN_E_NOT_READY;
+    const int half = (int)(c->n / 2);
+    for (uint32_t j = 0; j < count; ++j) {
+        const ocean_wave& w = rows[j];
+        for (float v : {w.kx, w.kz, w.ux, w.uz, w.re, w.im, w.omega})
+            if (!std::isfinite(v)) return OCEAN_E_INVALID;
+        if (w.jx < -half || w.jx >= half || w.jz < -half || w.jz >= half) return OCEAN_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));                        // nothing in flight may still read the set that is replaced
+    OCEAN_TRY(alloc_waves(c));
+    c->wave_count[tile] = 0;                       // (a copy that fails leaves no set, not a mixed one)
+    if (count) HIP_TRY(hipMemcpy(c->waves + (size_t)tile * WAVES_MAX, rows, count * sizeof(ocean_wave), hipMemcpyHostToDevice));
+    c->wave_count[tile] = count;
+    c->wave_length[tile] = c->prep_length[tile];
+    return OCEAN_OK;
+}
+
+int ocean_get_waves(ocean_t* c, uint32_t tile, ocean_wave* rows, uint32_t* count)
+{
+    if (!c || !count || tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!wave_set_exists(c, tile)) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    if (rows) HIP_TRY(hipMemcpy(rows, c->waves + (size_t)tile * WAVES_MAX, c->wave_count[tile] * sizeof(ocean_wave), hipMemcpyDeviceToHost));
+    *count = c->wave_count[tile];
+    return OCEAN_OK;
+}
+
+int ocean_eval_waves(ocean_t* c, const ocean_surface* s, float t, const float* xz, uint32_t points, float* out_pos, float* out_nrm)
+{
+    LastFrame f;
+    WaveEvalArgs a;
+    return staged_call(c, wave_eval_args(c, s, t, false, f, a), f, a, launch_waves<false>, points, xz, 2, out_pos, out_nrm, 2);
+}
+
+int ocean_eval_waves_device(ocean_t* c, const ocean_surface* s, float t, const void* d_xz, uint32_t points, void* d_out_pos, void* d_out_nrm)
+{
+    LastFrame f;
+    WaveEvalArgs a;
+    return device_call(c, wave_eval_args(c, s, t, false, f, a), f, a, launch_waves<false>, points, d_xz, d_out_pos, d_out_nrm, 2);
+}
+
+int ocean_query_waves(ocean_t* c, const ocean_surface* s, float t, const float* xz, uint32_t points, float* out_pos, float* out_nrm)
+{
+    LastFrame f;
+    WaveEvalArgs a;
+    return staged_call(c, wave_eval_args(c, s, t, true, f, a), f, a, launch_waves<true>, points, xz, 2, out_pos, out_nrm, 2);
+}
+
+int ocean_query_waves_device(ocean_t* c, const ocean_surface* s, float t, const void* d_xz, uint32_t points, void* d_out_pos, void* d_out_nrm)
+{
+    LastFrame f;
+    WaveEvalArgs a;
+    return device_call(c, wave_eval_args(c, s, t, true, f, a), f, a, launch_waves<true>, points, d_xz, d_out_pos, d_out_nrm, 2);
 }
 
 }  // extern "C"

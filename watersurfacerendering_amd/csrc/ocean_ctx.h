@@ -229,6 +229,16 @@ struct ocean_ctx {
     // Independent of the maps: kept across ocean_prepare / ocean_set_tile_size, freed by ocean_destroy.
     void* spray_scratch = nullptr;
     uint32_t spray_chunks = 0;
+    // Wave sets of the Gerstner proxy (ocean_extract_waves, ocean_set_waves): [tiles][4096] ocean_wave rows, of which tile i's first
+    // wave_count[i] are its set (0: none), with the tile length it was made for (N is the context's: a new tile size drops every set).
+    // wave_anim is the evaluation's per-call table ([8 cascades][4096][3] float4) and wave_scratch the selection's (histogram, counters, the
+    // list of survivors, the sorted bins): the consumer calls are ordered among themselves and the extraction drains everything first, so
+    // one of each serves.  All allocated on first use and freed by ocean_destroy; ocean_prepare and ocean_set_tile_size only drop the sets.
+    ocean_wave* waves = nullptr;
+    float4* wave_anim = nullptr;
+    unsigned* wave_scratch = nullptr;
+    std::vector<uint32_t> wave_count;
+    std::vector<float> wave_length;
     unsigned long long* stamps = nullptr;   // diagnostic builds only
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
