@@ -684,6 +684,144 @@ int ocean_query_waves(ocean_t* ctx, const ocean_surface* s, float t, const float
 int ocean_query_waves_device(ocean_t* ctx, const ocean_surface* s, float t, const void* d_xz, uint32_t points,
                              void* d_out_pos, void* d_out_nrm);
 
+/* ---- fragment stage: Preetham sky and the reference's water colour ---------------------------------------------------------------------
+ * Everything above produces what the reference's VERTEX shader produces; these calls are its fragment stage (SkyPreetham::Update,
+ * SkyPreetham.frag, WaterSurfaceMesh.frag) as a pure per-point function: no camera model, no march, no image geometry.  They take the
+ * (position, normal) rows ocean_displace_grid*, ocean_query_surface, ocean_raycast_surface, ocean_sample_surface_lod and ocean_eval_waves
+ * write and return radiance.  Per-frame order: frame -> ocean_displace_grid* -> ocean_shade_grid; or ocean_raycast_surface(_device) ->
+ * ocean_shade_points(_device) with foam_white = 0 (a hit's w is t, not the Jacobian): a render in two calls.
+ * Sky, host   ocean_sky_coefficients restates SkyPreetham::Update.  A pure host function: no context.  turbidity T and sun_dir are fp32
+ *          inputs; everything below is evaluated in double and each output is rounded to fp32 once.
+ *            sun = sun_dir / |sun_dir|;   thetaSun = acos(max(sun.y, 0))
+ *            A = ( 0.1787 T - 1.4630, -0.0193 T - 0.2592, -0.0167 T - 0.2608)      (per channel of Yxy)
+ *            B = (-0.3554 T + 0.4275, -0.0665 T + 0.0008, -0.0950 T + 0.0092)
+ *            C = (-0.0227 T + 5.3251, -0.0004 T + 0.2125, -0.0079 T + 0.2102)
+ *            D = ( 0.1206 T - 2.5771, -0.0641 T - 0.8989, -0.0441 T - 1.6537)
+ *            E = (-0.0670 T + 0.3703, -0.0033 T + 0.0452, -0.0109 T + 0.0529)
+ *            chi = (4/9 - T/120) (pi - 2 thetaSun);   Yz = (4.0453 T - 4.9710) tan(chi) - 0.2155 T + 2.4192
+ *            xz = ( 0.00165 th^3 - 0.00375 th^2 + 0.00209 th          ) T^2 + (-0.02903 th^3 + 0.06377 th^2 - 0.03202 th + 0.00394) T
+ *               + ( 0.11693 th^3 - 0.21196 th^2 + 0.06052 th + 0.25886)                                              (th = thetaSun)
+ *            yz = ( 0.00275 th^3 - 0.00610 th^2 + 0.00317 th          ) T^2 + (-0.04214 th^3 + 0.08970 th^2 - 0.04153 th + 0.00516) T
+ *               + ( 0.15346 th^3 - 0.26756 th^2 + 0.06670 th + 0.26688)
+ *            ZenithLum = (Yz, xz, yz);   ZeroThetaSun = (1 + A exp(B / cos 0)) (1 + C exp(D thetaSun) + E cos^2 thetaSun)
+ *          ocean_sky_coeffs has the layout of the uniform block the reference uploads (SkyPreetham::Props: a float3 and the turbidity, then
+ *          seven float3 padded to 16 bytes, 128 bytes): a Vulkan host fills its UBO from it.  The padding words are 0.
+ * Sky, device  ocean_sky_radiance evaluates SkyPreetham.frag for `count` view directions; fp32, the device's full-precision expf / acosf /
+ *          cosf; the optics are held to a derived bound (tests/shading.py), not to bits.  d = dir / |dir|, then SKY(d):
+ *            thetaView = acosf(clamp(d.y, 0, 1));   cg = clamp(dot(sun, d), 0, 1);   gamma = acosf(cg)
+ *            (the upper clamp is ours: two fp32 unit vectors can have a dot product of 1 + an ulp, and acosf of that is NaN)
+ *            F = (1 + A expf(B / (cosf(thetaView) + 1e-3f))) (1 + C expf(D gamma) + E cosf(gamma)^2)        (per channel; kBias = 1e-3f)
+ *            (Y, x, y) = ZenithLum (F / ZeroThetaSun)          (the quotient ZenithLum / ZeroThetaSun is formed once, on the host)
+ *            X = x (Y / y),  Z = (1 - x - y) (Y / y)
+ *            L = ( 2.3706743 X - 0.9000405 Y - 0.4706338 Z,            (CIE-E, the shader's XYZ * M)
+ *                 -0.5138850 X + 1.4253036 Y + 0.0885814 Z,
+ *                  0.0052982 X - 0.0146949 Y + 1.0093968 Z)
+ *            disk = smoothstep(0.997f, 1.0f, cg):  s = clamp((cg - 0.997f) / (1.0f - 0.997f), 0, 1),  disk = s s (3 - 2 s)
+ *          out = (L 0.05f + (sun_color disk) L,  disk), not tone-mapped.  Needs a context for the stream and the staging only: neither
+ *          Prepare nor a frame.  dirs[3*count] are 4-byte aligned, out[4*count] 16-byte aligned in the device form.
+ * Seabed   ocean_eval_seabed evaluates the reference's procedural seabed (WaterSurfaceMesh.frag: TerrainNormal, TerrainColor) at terrain
+ *          points p = (x, z): out = (n.x, n.y, n.z, colour factor).  fp32 throughout, NO contraction, fract(a) = a - floorf(a), in exactly
+ *          this order (tests/shading.py repeats it step for step in float32 and the device is held to it in every bit):
+ *            hash1(ix, iy):  jx = 50.0f * fract(ix * 0.31830987f);  jy = 50.0f * fract(iy * 0.31830987f)       (0.31830987f = (float)(1/pi))
+ *                            = fract((jx * jy) * (jx + jy))
+ *            noise(px, py):  ix = floorf(px), fx = px - ix;  iy, fy likewise
+ *                            ux = ((fx * fx) * fx) * (fx * (fx * 6.0f - 15.0f) + 10.0f);  uy likewise                 (quintic)
+ *                            a = hash1(ix, iy), b = hash1(ix + 1.0f, iy), c = hash1(ix, iy + 1.0f), d = hash1(ix + 1.0f, iy + 1.0f)
+ *                            = -1.0f + 2.0f * (((a + (b - a) * ux) + (c - a) * uy) + ((((a - b) - c) + d) * ux) * uy)
+ *            fbm4(px, py):   v = 0.0f, g = 0.5f; four times:  v = v + g * noise(px, py);  g = g * 0.5f;
+ *                            (px, py) = (1.6f * px + 1.2f * py,  -1.2f * px + 1.6f * py)
+ *            H(x, z)       = 0.0f - 8.0f * fbm4(z * 0.02f, x * 0.02f)                                        (the shader's p.yx)
+ *            factor        = fminf(fmaxf(fbm4((z * 0.02f) * 2.0f, (x * 0.02f) * 2.0f), 0.6f), 0.9f)
+ *            e = 1e-4f;  nx = H(x - e, z) - H(x + e, z);  ny = 10.0f * e;  nz = H(x, z - e) - H(x, z + e)
+ *            len = sqrtf((nx * nx + ny * ny) + nz * nz);  n = (nx / len, ny / len, nz / len)
+ *          It is its own entry point because it is the one part of the fragment stage that CAN be held to bits and the one that cannot be
+ *          compared with float64 at all: hash1 resolves 2^-7 at its largest arguments, and a few hundred metres out e is below the ulp of
+ *          p, where the finite difference is 0 and the normal (0, 1, 0).  A renderer that draws the seabed takes its colour from here:
+ *          factor * terrain_color.  xz[2*count] 8-byte, out 16-byte aligned in the device form.  No Prepare, no frame.
+ * Water    ocean_water is the reference's WaterSurfaceUBO without the sky, and four switches.  ocean_shade_points, per point, in the
+ *          shader's order; fp32, may contract, held to the derived bound:
+ *            d = normalize(pos.xyz - cam_pos)       (the ray goes to the UNRAISED position, as the reference's main does)
+ *            n = normalize(nrm.xyz);   p_w = (pos.x, pos.y + height, pos.z);   V = -d
+ *            r = d - 2 dot(n, d) n;    S = L 0.05f + disk L  with (L, disk) = SKY(r), r as it is: the water shader's SkyLuminance, whose
+ *                                      disk is not multiplied by sun_color
+ *            L_a = sky_intensity max(dot(n, sun), 0) S
+ *            Hw = normalize(sun + V);  L_s = sun_intensity (specular_intensity clamp(powf(max(dot(n, Hw), 0), specular_highlights), 0, 1)) S
+ *            refr = GLSL refract(-sun, n, eta), eta = 1 / 1.33477:  c = dot(n, -sun),  k = 1 - eta^2 (1 - c^2),
+ *                                      refr = eta (-sun) - (eta c + sqrtf(k)) n, or 0 where k < 0        (the SUN's ray, not the view's)
+ *            t_g = -p_w.y / refr.y  (the plane y = 0);   p_g = p_w + t_g refr
+ *            (n_g, factor) = the seabed above at (p_g.x, p_g.z)  (OCEAN_SEABED_REFERENCE)  or  ((0, 1, 0), seabed_factor)  (OCEAN_SEABED_FLAT)
+ *            L_g = factor terrain_color dot(n_g, -refr)
+ *            L_df0 = ((0.33 backscatter) / absorb) ((pi L_a) (1 / pi))                        (the quotient is formed once, on the host)
+ *            Att(dist, depth) = expf(-(absorb 0.1) dist - (scatter 0.1) depth)                (the 0.1-scaled coefficients likewise)
+ *            L_u = Att(t_g, 0) L_g + (1 - Att(t_g, |p_w.y - p_g.y|)) L_df0
+ *            F_r, OCEAN_FRESNEL_REFERENCE: the shader as shipped.  ti = dot(n, V) and tt = dot(-n, refr) -- two COSINES, the second of the
+ *                   sun's refraction angle -- go into a formula written for angles:  ti <= 1e-5f -> ((ior - 1) / (ior + 1))^2 (rounded once
+ *                   on the host), otherwise 0.5 (t1^2 + t2^2), t1 = sinf(ti - tt) / sinf(ti + tt), t2 = tanf(ti - tt) / tanf(ti + tt)
+ *            F_r, OCEAN_FRESNEL_PHYSICAL:  ci = dot(n, V);  ci <= 0 -> 1;  ct = sqrtf(1 - (1 - ci^2) / ior^2),
+ *                   rs = (ci - ior ct) / (ci + ior ct),  rp = (ior ci - ct) / (ior ci + ct),  F_r = 0.5 (rs^2 + rp^2)
+ *            colour = F_r (L_s + L_a) + (1 - F_r) L_u;   foam_white and pos.w < 0 -> colour = (1, 1, 1)     (the reference's main)
+ *            out_rgba = (colour, 1.0f);   tonemap -> 1 - expf(-2 c) on all four channels
+ *            out_aux  = (p_g.x, p_g.z, t_g, F_r): the seabed hit and the reflectance (may be NULL)
+ *          Supported range: the row of a point is unspecified where the restated colour is not finite -- a zero normal, pos == cam_pos,
+ *          refr.y >= 0, a non-finite input -- and such a point disturbs no other row.
+ * The grid ocean_shade_grid shades the context's vertex-stage output -- the buffers ocean_device_grid hands out, from the most recent
+ *          ocean_displace_grid, _cascades or _lod -- into a context-owned (grid_size+1)^2 float4 image, stream-ordered behind that vertex
+ *          stage, with the kernel of ocean_shade_points: the same grid through ocean_shade_points_device gives the same bits.  The image
+ *          grows on demand (a growth that fails leaves nothing behind) and goes with ocean_destroy.  ocean_read_shaded copies it out
+ *          (synchronises); ocean_device_shaded hands out the pointer (NULL while there is none) and the vertex count.
+ *          OCEAN_E_NOT_READY when no grid has been displaced since ocean_prepare, and for the read without a shaded image.
+ * Host / device forms, staging, stream order (ocean_stream) and alignment as ocean_sample_surface_lod / _device: the host forms stage
+ * [outputs | inputs] in the context's buffer and return when the results are there; the device forms are enqueued and return at once.
+ * Errors: OCEAN_E_INVALID for a NULL context, structure or -- with count > 0 -- array (out_aux excepted); a field that is not finite; a
+ * zero sun vector; a turbidity outside [1, 10]; absorb <= 0; specular_highlights <= 0; an unknown fresnel or seabed.  count == 0
+ * returns OCEAN_OK before the pointers are looked at.  The reference's three quirks are kept on purpose and named in INTEGRATION.md E12:
+ * cosines passed as angles, the sun's refraction angle in Fresnel, the ray to the unraised position.
+ * (An addition to ABI version 5: nothing of the existing entry points or structures changes.)                                            */
+enum { OCEAN_FRESNEL_REFERENCE = 0, OCEAN_FRESNEL_PHYSICAL = 1 };
+enum { OCEAN_SEABED_REFERENCE = 0, OCEAN_SEABED_FLAT = 1 };
+typedef struct ocean_sky {
+    float sun_dir[3];                  /* towards the sun; normalised by the call                     default (0, 0.5, 0.866) */
+    float turbidity;                   /* 1 .. 10                                                     default 2.5 */
+    float sun_color[3];                /*                                                             default (1, 1, 1) */
+    float sun_intensity;               /*                                                             default 1 */
+} ocean_sky;
+typedef struct ocean_sky_coeffs {      /* 32 words, 128 bytes: SkyPreetham::Props as uploaded; every fourth word of the float3s is 0 */
+    float sun_dir[3];                  /* normalised */
+    float turbidity;
+    float A[4], B[4], C[4], D[4], E[4];
+    float zenith_lum[4];               /* (Y, x, y) of the zenith */
+    float zero_theta_sun[4];
+} ocean_sky_coeffs;
+typedef struct ocean_water {
+    float    cam_pos[3];               /*                                                             default (0, 60, 0) */
+    float    height;                   /* of the water plane above the seabed's y = 0                 default 50 */
+    float    absorb[3];                /* 1/m at 680 / 550 / 440 nm, > 0: Jerlov I                    default (0.420, 0.063, 0.019) */
+    float    scatter[3];               /* b(514 nm) = 0.037 through (-0.00113 nm + 1.62517) / (-0.00113 * 514 + 1.62517) */
+    float    backscatter[3];           /* 0.01829 scatter + 0.00006 */
+    float    terrain_color[3];         /*                                                             default (0.964, 1.0, 0.824) */
+    float    sky_intensity, specular_intensity, specular_highlights;      /* highlights > 0           default 1, 1, 32 */
+    uint32_t fresnel;                  /* OCEAN_FRESNEL_*                                             default REFERENCE */
+    uint32_t seabed;                   /* OCEAN_SEABED_*                                              default REFERENCE */
+    float    seabed_factor;            /* colour factor of OCEAN_SEABED_FLAT                          default 0.75 */
+    uint32_t foam_white;               /* pos.w < 0 paints (1, 1, 1); 0 for ray-cast hits             default 1 */
+    uint32_t tonemap;                  /* 1 - exp(-2 c) on all four channels                          default 1 */
+} ocean_water;
+
+void ocean_default_sky(ocean_sky* s);
+void ocean_default_water(ocean_water* w);
+int ocean_sky_coefficients(const ocean_sky* s, ocean_sky_coeffs* out);
+int ocean_sky_radiance(ocean_t* ctx, const ocean_sky* s, const float* dirs /* 3 * count */, uint32_t count, float* out /* 4 * count */);
+int ocean_sky_radiance_device(ocean_t* ctx, const ocean_sky* s, const void* d_dirs, uint32_t count, void* d_out);
+int ocean_eval_seabed(ocean_t* ctx, const float* xz /* 2 * count */, uint32_t count, float* out /* 4 * count */);
+int ocean_eval_seabed_device(ocean_t* ctx, const void* d_xz, uint32_t count, void* d_out);
+int ocean_shade_points(ocean_t* ctx, const ocean_sky* s, const ocean_water* w, const float* pos /* 4 * count */,
+                       const float* nrm /* 4 * count */, uint32_t count, float* out_rgba /* 4 * count */, float* out_aux /* may be NULL */);
+int ocean_shade_points_device(ocean_t* ctx, const ocean_sky* s, const ocean_water* w, const void* d_pos, const void* d_nrm,
+                              uint32_t count, void* d_out_rgba, void* d_out_aux /* may be NULL */);
+int ocean_shade_grid(ocean_t* ctx, const ocean_sky* s, const ocean_water* w);
+int ocean_read_shaded(ocean_t* ctx, float* rgba /* 4 * vertices */);
+int ocean_device_shaded(ocean_t* ctx, void** d_rgba, uint32_t* vertices);
+
 #ifdef __cplusplus
 }
 #endif

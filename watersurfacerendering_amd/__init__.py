@@ -28,7 +28,8 @@ import numpy as np
 from . import _abi
 from ._abi import OceanError, Params, build  # noqa: F401
 
-__all__ = ["WSTessendorf", "OceanBatch", "OceanError", "build", "host_register", "host_unregister", "comm_unique_id", "BODY_DTYPE", "WAVE_DTYPE"]
+__all__ = ["WSTessendorf", "OceanBatch", "OceanError", "build", "host_register", "host_unregister", "comm_unique_id", "BODY_DTYPE", "WAVE_DTYPE",
+           "sky_params", "water_params", "sky_coefficients"]
 
 #: struct ocean_body (include/ocean_consumers.h) as a numpy record: what OceanBatch.buoyancy takes
 BODY_DTYPE = np.dtype([("pos", np.float32, 3), ("quat", np.float32, 4), ("vel", np.float32, 3), ("omega", np.float32, 3),
@@ -37,6 +38,52 @@ BODY_DTYPE = np.dtype([("pos", np.float32, 3), ("quat", np.float32, 4), ("vel", 
 #: struct ocean_wave (include/ocean_consumers.h) as a numpy record: what OceanBatch.extract_waves returns and set_waves takes
 WAVE_DTYPE = np.dtype([("jx", np.int32), ("jz", np.int32), ("kx", np.float32), ("kz", np.float32), ("ux", np.float32), ("uz", np.float32),
                        ("re", np.float32), ("im", np.float32), ("omega", np.float32), ("bin", np.uint32), ("reserved", np.float32, 2)])
+
+
+def _dev_ptr(x):
+    """A device array as the C ABI takes it: a torch tensor's data_ptr(), an integer address, or None."""
+    if x is None:
+        return None
+    return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
+
+
+def _patched(struct, fields):
+    for k, v in fields.items():
+        kind = dict(struct._fields_).get(k)
+        if kind is None:
+            raise TypeError(f"unknown field {k!r} of {type(struct).__name__}")
+        if kind is C.c_uint32:
+            setattr(struct, k, int(v))
+        elif kind is C.c_float:
+            setattr(struct, k, float(v))
+        else:
+            setattr(struct, k, kind(*[float(x) for x in v]))
+    return struct
+
+
+def sky_params(**fields) -> "_abi.Sky":
+    """struct ocean_sky with the reference's defaults (ocean_default_sky), patched by sun_dir / turbidity / sun_color / sun_intensity."""
+    s = _abi.Sky()
+    _abi.lib().ocean_default_sky(C.byref(s))
+    return _patched(s, fields)
+
+
+def water_params(**fields) -> "_abi.Water":
+    """struct ocean_water with the reference's defaults (ocean_default_water), patched by any of its fields (cam_pos, height, absorb,
+    scatter, backscatter, terrain_color, sky_intensity, specular_intensity, specular_highlights, fresnel, seabed, seabed_factor,
+    foam_white, tonemap)."""
+    w = _abi.Water()
+    _abi.lib().ocean_default_water(C.byref(w))
+    return _patched(w, fields)
+
+
+def sky_coefficients(sky=None) -> "_abi.SkyCoeffs":
+    """SkyPreetham::Update on the host (ocean_sky_coefficients): the normalised sun, the turbidity and A, B, C, D, E, ZenithLum,
+    ZeroThetaSun in the layout of the reference's uniform block.  Needs neither a context nor a device."""
+    k = _abi.SkyCoeffs()
+    s = sky_params() if sky is None else sky
+    _abi.check(_abi.lib().ocean_sky_coefficients(C.byref(s), C.byref(k)), "ocean_sky_coefficients")
+    return k
 
 
 def _is_pow2(n: int) -> bool:
@@ -796,6 +843,85 @@ class OceanBatch:
         s = self._surface(first_tile, uv_scales, grid_size, vertex_distance, choppy, iterations)
         _abi.check(self._L.ocean_query_waves_device(self._h, C.byref(s), float(t), C.c_void_p(d_xz), int(points), C.c_void_p(d_pos),
                                                     C.c_void_p(d_nrm)), "ocean_query_waves_device")
+
+    # -- fragment stage (include/ocean_consumers.h: ocean_sky_radiance, ocean_eval_seabed, ocean_shade_points, ocean_shade_grid) ------------
+    def device_grid(self):
+        """(d_positions, d_normals, vertices) of the vertex stage's output buffers (ocean_device_grid): what shade_grid shades."""
+        d, q, v = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+        _abi.check(self._L.ocean_device_grid(self._h, C.byref(d), C.byref(q), C.byref(v)), "ocean_device_grid")
+        return d.value, q.value, v.value
+
+    def sky_radiance(self, dirs, sky=None):
+        """SkyPreetham.frag for view directions dirs [count, 3] (ocean_sky_radiance; normalised by the call): (count, 4) float32,
+        (r, g, b, sun disk), not tone-mapped.  sky: a struct from sky_params(), or None for the defaults.  Needs no Prepare."""
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.empty((d.shape[0], 4), dtype=np.float32)
+        s = sky_params() if sky is None else sky
+        _abi.check(self._L.ocean_sky_radiance(self._h, C.byref(s), d.ctypes.data_as(C.c_void_p), d.shape[0], out.ctypes.data_as(C.c_void_p)),
+                   "ocean_sky_radiance")
+        return out
+
+    def sky_radiance_device(self, d_dirs, count: int, d_out, sky=None):
+        """sky_radiance on device arrays (ocean_sky_radiance_device): torch tensors or pointers, dirs [count][3], out [count][4] float32."""
+        s = sky_params() if sky is None else sky
+        _abi.check(self._L.ocean_sky_radiance_device(self._h, C.byref(s), _dev_ptr(d_dirs), int(count), _dev_ptr(d_out)), "ocean_sky_radiance_device")
+
+    def eval_seabed(self, xz):
+        """The reference's procedural seabed at terrain points xz [count, 2] (ocean_eval_seabed): (count, 4) float32, (unit normal,
+        colour factor in [0.6, 0.9]).  Needs no Prepare."""
+        q = np.ascontiguousarray(xz, dtype=np.float32).reshape(-1, 2)
+        out = np.empty((q.shape[0], 4), dtype=np.float32)
+        _abi.check(self._L.ocean_eval_seabed(self._h, q.ctypes.data_as(C.c_void_p), q.shape[0], out.ctypes.data_as(C.c_void_p)), "ocean_eval_seabed")
+        return out
+
+    def eval_seabed_device(self, d_xz, count: int, d_out):
+        """eval_seabed on device arrays (ocean_eval_seabed_device): torch tensors or pointers, xz [count][2], out [count][4] float32."""
+        _abi.check(self._L.ocean_eval_seabed_device(self._h, _dev_ptr(d_xz), int(count), _dev_ptr(d_out)), "ocean_eval_seabed_device")
+
+    def shade_points(self, pos, nrm, sky=None, water=None, aux: bool = False):
+        """The reference's water colour for (position, normal) rows [count, 4] as the vertex stage, the queries and the ray cast write
+        them (ocean_shade_points): rgba (count, 4) float32, and with aux=True also (p_g.x, p_g.z, t_g, F_r) per point.  sky / water:
+        structs from sky_params() / water_params(), or None for the reference's defaults."""
+        p = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 4)
+        n = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 4)
+        if p.shape != n.shape:
+            raise ValueError("pos and nrm: the same number of rows")
+        rgba = np.empty_like(p)
+        ax = np.empty_like(p) if aux else None
+        s = sky_params() if sky is None else sky
+        w = water_params() if water is None else water
+        _abi.check(self._L.ocean_shade_points(self._h, C.byref(s), C.byref(w), p.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p),
+                                              p.shape[0], rgba.ctypes.data_as(C.c_void_p), ax.ctypes.data_as(C.c_void_p) if aux else None),
+                   "ocean_shade_points")
+        return (rgba, ax) if aux else rgba
+
+    def shade_points_device(self, d_pos, d_nrm, count: int, d_rgba, d_aux=None, sky=None, water=None):
+        """shade_points on device arrays (ocean_shade_points_device): torch tensors or pointers, [count][4] float32 each, 16-byte aligned;
+        d_aux may be None.  Enqueued on the consumers' stream (`stream`); returns at once."""
+        s = sky_params() if sky is None else sky
+        w = water_params() if water is None else water
+        _abi.check(self._L.ocean_shade_points_device(self._h, C.byref(s), C.byref(w), _dev_ptr(d_pos), _dev_ptr(d_nrm), int(count),
+                                                     _dev_ptr(d_rgba), _dev_ptr(d_aux)), "ocean_shade_points_device")
+
+    def shade_grid(self, sky=None, water=None):
+        """Shade the vertex stage's output -- the most recent displace_grid, _cascades or _lod -- into the context's image
+        (ocean_shade_grid).  Enqueued behind that vertex stage; read_shaded copies the image out."""
+        s = sky_params() if sky is None else sky
+        w = water_params() if water is None else water
+        _abi.check(self._L.ocean_shade_grid(self._h, C.byref(s), C.byref(w)), "ocean_shade_grid")
+
+    def device_shaded(self):
+        """(d_rgba, vertices) of the shaded image (ocean_device_shaded); (None, 0) while there is none."""
+        d, v = C.c_void_p(), C.c_uint32(0)
+        _abi.check(self._L.ocean_device_shaded(self._h, C.byref(d), C.byref(v)), "ocean_device_shaded")
+        return d.value, v.value
+
+    def read_shaded(self) -> np.ndarray:
+        """The shaded image as (vertices, 4) float32 (ocean_read_shaded).  Synchronises."""
+        _, v = self.device_shaded()
+        out = np.empty((max(v, 1), 4), dtype=np.float32)
+        _abi.check(self._L.ocean_read_shaded(self._h, out.ctypes.data_as(C.c_void_p)), "ocean_read_shaded")
+        return out[:v]
 
     def export_maps(self):
         """dma-buf of the current map set (ocean_export_maps): (fd, disp_offset, nrm_offset, bytes, map_set); close the fd yourself."""

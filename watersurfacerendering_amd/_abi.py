@@ -29,6 +29,8 @@ OCEAN_NO_SOURCE = 0xFFFFFFFF       # ocean_set_velocity_twin: an ordinary tile
 OCEAN_MODE_FULL7, OCEAN_MODE_CHOPPY5, OCEAN_MODE_HEIGHT1, OCEAN_MODE_JACOBIAN = 0, 1, 2, 3
 OCEAN_SPECTRUM_PHILLIPS, OCEAN_SPECTRUM_PM, OCEAN_SPECTRUM_JONSWAP, OCEAN_SPECTRUM_TMA = 0, 1, 2, 3     # ocean_spectrum.kind
 OCEAN_SPREAD_COS2S, OCEAN_SPREAD_HASSELMANN = 0, 1                                                      # ocean_spectrum.spreading
+OCEAN_FRESNEL_REFERENCE, OCEAN_FRESNEL_PHYSICAL = 0, 1                                                  # ocean_water.fresnel
+OCEAN_SEABED_REFERENCE, OCEAN_SEABED_FLAT = 0, 1                                                        # ocean_water.seabed
 
 #: every symbol the library's three headers declare (tests check the .so exports each one, and that each list equals its header's)
 SYMBOLS_BOUNDARY = [        # include/ocean.h: the drop-in boundary
@@ -56,6 +58,9 @@ SYMBOLS_CONSUMERS = [       # include/ocean_consumers.h: SURVEY.md 8f ranks 3-4
     "ocean_default_spray", "ocean_emit_spray", "ocean_emit_spray_device",
     "ocean_default_spectrum", "ocean_set_spectrum", "ocean_get_spectrum", "ocean_spectrum_moments",
     "ocean_extract_waves", "ocean_set_waves", "ocean_get_waves", "ocean_eval_waves", "ocean_eval_waves_device", "ocean_query_waves", "ocean_query_waves_device",
+    "ocean_default_sky", "ocean_default_water", "ocean_sky_coefficients", "ocean_sky_radiance", "ocean_sky_radiance_device",
+    "ocean_eval_seabed", "ocean_eval_seabed_device", "ocean_shade_points", "ocean_shade_points_device",
+    "ocean_shade_grid", "ocean_read_shaded", "ocean_device_shaded",
 ]
 SYMBOLS_DEV = [             # include/ocean_dev.h: tests, bench.py, tools/
     "ocean_read_spectrum", "ocean_read_xi",
@@ -147,6 +152,25 @@ class Wave(C.Structure):
     """struct ocean_wave (include/ocean_consumers.h): one spectrum bin of a tile's wave set; 12 words."""
     _fields_ = [("jx", C.c_int32), ("jz", C.c_int32), ("kx", C.c_float), ("kz", C.c_float), ("ux", C.c_float), ("uz", C.c_float),
                 ("re", C.c_float), ("im", C.c_float), ("omega", C.c_float), ("bin", C.c_uint32), ("reserved", C.c_float * 2)]
+
+
+class Sky(C.Structure):
+    """struct ocean_sky (include/ocean_consumers.h): the sun and the turbidity of the Preetham sky."""
+    _fields_ = [("sun_dir", C.c_float * 3), ("turbidity", C.c_float), ("sun_color", C.c_float * 3), ("sun_intensity", C.c_float)]
+
+
+class SkyCoeffs(C.Structure):
+    """struct ocean_sky_coeffs (include/ocean_consumers.h): the reference's sky uniform block; 32 words."""
+    _fields_ = [("sun_dir", C.c_float * 3), ("turbidity", C.c_float), ("A", C.c_float * 4), ("B", C.c_float * 4), ("C", C.c_float * 4),
+                ("D", C.c_float * 4), ("E", C.c_float * 4), ("zenith_lum", C.c_float * 4), ("zero_theta_sun", C.c_float * 4)]
+
+
+class Water(C.Structure):
+    """struct ocean_water (include/ocean_consumers.h): the reference's WaterSurfaceUBO without the sky, and the four switches."""
+    _fields_ = [("cam_pos", C.c_float * 3), ("height", C.c_float), ("absorb", C.c_float * 3), ("scatter", C.c_float * 3),
+                ("backscatter", C.c_float * 3), ("terrain_color", C.c_float * 3), ("sky_intensity", C.c_float),
+                ("specular_intensity", C.c_float), ("specular_highlights", C.c_float), ("fresnel", C.c_uint32), ("seabed", C.c_uint32),
+                ("seabed_factor", C.c_float), ("foam_white", C.c_uint32), ("tonemap", C.c_uint32)]
 
 
 last_build = ""      # what the most recent build() did, for the caller to log
@@ -329,6 +353,18 @@ def lib() -> C.CDLL:
         "ocean_eval_waves_device": (i32, [P, C.POINTER(Surface), f32, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_query_waves": (i32, [P, C.POINTER(Surface), f32, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
         "ocean_query_waves_device": (i32, [P, C.POINTER(Surface), f32, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_default_sky": (None, [C.POINTER(Sky)]),
+        "ocean_default_water": (None, [C.POINTER(Water)]),
+        "ocean_sky_coefficients": (i32, [C.POINTER(Sky), C.POINTER(SkyCoeffs)]),
+        "ocean_sky_radiance": (i32, [P, C.POINTER(Sky), C.c_void_p, u32, C.c_void_p]),
+        "ocean_sky_radiance_device": (i32, [P, C.POINTER(Sky), C.c_void_p, u32, C.c_void_p]),
+        "ocean_eval_seabed": (i32, [P, C.c_void_p, u32, C.c_void_p]),
+        "ocean_eval_seabed_device": (i32, [P, C.c_void_p, u32, C.c_void_p]),
+        "ocean_shade_points": (i32, [P, C.POINTER(Sky), C.POINTER(Water), C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_shade_points_device": (i32, [P, C.POINTER(Sky), C.POINTER(Water), C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p]),
+        "ocean_shade_grid": (i32, [P, C.POINTER(Sky), C.POINTER(Water)]),
+        "ocean_read_shaded": (i32, [P, C.c_void_p]),
+        "ocean_device_shaded": (i32, [P, C.POINTER(C.c_void_p), C.POINTER(u32)]),
         "ocean_set_mode": (i32, [P, i32]),
         "ocean_set_dispersion": (i32, [P, i32, f32]),
         "ocean_set_spectrum_precision": (i32, [P, i32]),

@@ -1,6 +1,6 @@
 // ocean_consumers.hip -- host side of include/ocean_consumers.h: what reads the maps of the most recent frame on the device (vertex stage and
 // cascades, mip chain, surface query, ray cast, persistent foam, buoyancy, water velocity, LOD sampling, surface bounds, spray emitters) and the device memory those calls own -- and the Gerstner proxy, which reads the prepared spectrum instead.  Their kernels:
-// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h, ocean_bounds_kernels.h, ocean_spray_kernels.h, ocean_waves_kernels.h.  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
+// ocean_consumer_kernels.h, ocean_foam_kernels.h, ocean_velocity_kernels.h, ocean_buoyancy_kernels.h, ocean_lod_kernels.h, ocean_bounds_kernels.h, ocean_spray_kernels.h, ocean_waves_kernels.h, ocean_shading_kernels.h (the fragment stage: sky, seabed, water colour, which read no map either).  What it shares with ocean_api.hip is at the end of ocean_ctx.h.  No CPU fallback here either.
 #include <algorithm>
 #include <cmath>
 
@@ -11,6 +11,7 @@
 #include "ocean_bounds_kernels.h"
 #include "ocean_spray_kernels.h"
 #include "ocean_waves_kernels.h"
+#include "ocean_shading_kernels.h"
 
 using namespace ocean;
 
@@ -89,7 +90,7 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     c->foam_cur = 0; c->foam_ready = false;
     // the grid and mip buffers survive a new tile size (the grid's does not depend on it, ocean_build_mips re-allocates for mips_n != n),
     // their contents do not: they were made from maps that are gone
-    c->mips_ready = false; c->grid_vertices = 0;
+    c->mips_ready = false; c->grid_vertices = 0; c->grid_fresh = false; c->shaded_vertices = 0;
     c->lod_ready = false;           // (the set of ocean_build_mips_tiles likewise: its capacity is in texels, whatever the tile size)
     c->bnd_ready = false;           // (... and that of ocean_build_bounds_tiles)
     std::fill(c->wave_count.begin(), c->wave_count.end(), 0u);      // (the wave sets name bins of a lattice that is gone; their buffers stay)
@@ -101,6 +102,7 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     free_and_null(c->hull); c->hull_points = 0;
     free_and_null(c->spray_scratch); c->spray_chunks = 0;
     free_and_null(c->waves); free_and_null(c->wave_anim); free_and_null(c->wave_scratch);
+    free_and_null(c->shaded); c->shaded_capacity = 0;
     if (c->consumer_ev) { (void)hipEventDestroy(c->consumer_ev); c->consumer_ev = nullptr; }
     c->consumer_pending = false;
 }
@@ -135,7 +137,7 @@ int ocean_displace_grid(ocean_t* c, uint32_t tile, uint32_t grid_size, float ver
     hipLaunchKernelGGL(k_displace_grid, dim3((verts + 255) / 256), dim3(256), 0, f.st, g);
     HIP_TRY(hipGetLastError());
     OCEAN_TRY(consumer_end(c, f.st));
-    c->grid_vertices = verts;
+    c->grid_vertices = verts; c->grid_fresh = true;
     return OCEAN_OK;
 }
 
@@ -155,7 +157,7 @@ int ocean_displace_grid_cascades(ocean_t* c, uint32_t first_tile, uint32_t count
     hipLaunchKernelGGL(k_displace_grid_cascades, dim3((verts + 255) / 256), dim3(256), 0, f.st, a);
     HIP_TRY(hipGetLastError());
     OCEAN_TRY(consumer_end(c, f.st));
-    c->grid_vertices = verts;
+    c->grid_vertices = verts; c->grid_fresh = true;
     return OCEAN_OK;
 }
 
@@ -548,7 +550,7 @@ int ocean_displace_grid_lod(ocean_t* c, uint32_t first_tile, uint32_t count, uin
     hipLaunchKernelGGL(k_displace_grid_lod, dim3((verts + 255) / 256), dim3(256), 0, f.st, a);
     HIP_TRY(hipGetLastError());
     OCEAN_TRY(consumer_end(c, f.st));
-    c->grid_vertices = verts;
+    c->grid_vertices = verts; c->grid_fresh = true;
     return OCEAN_OK;
 }
 
@@ -1310,6 +1312,302 @@ int ocean_query_waves_device(ocean_t* c, const ocean_surface* s, float t, const 
     LastFrame f;
     WaveEvalArgs a;
     return device_call(c, wave_eval_args(c, s, t, true, f, a), f, a, launch_waves<true>, points, d_xz, d_out_pos, d_out_nrm, 2);
+}
+
+}  // extern "C"
+
+// ---- fragment stage (include/ocean_consumers.h): Preetham sky, the reference's seabed and water colour ---------------------------------------
+static bool all_finite(const float* v, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// SkyPreetham::Update in double: the normalised sun and A, B, C, D, E, ZenithLum, ZeroThetaSun per channel of Yxy.
+static int sky_double(const ocean_sky* s, double sun[3], double co[7][3])
+{
+    if (!s || !all_finite(s->sun_dir, 3) || !all_finite(s->sun_color, 3) || !std::isfinite(s->turbidity) || !std::isfinite(s->sun_intensity))
+        return OCEAN_E_INVALID;
+    const double x = s->sun_dir[0], y = s->sun_dir[1], z = s->sun_dir[2], len = std::sqrt(x * x + y * y + z * z);
+    if (!(len > 0.0) || !(s->turbidity >= 1.0f && s->turbidity <= 10.0f)) return OCEAN_E_INVALID;
+    sun[0] = x / len; sun[1] = y / len; sun[2] = z / len;
+    const double t = s->turbidity, th = std::acos(std::max(sun[1], 0.0));
+    const double A[3] = {0.1787 * t - 1.4630, -0.0193 * t - 0.2592, -0.0167 * t - 0.2608};
+    const double B[3] = {-0.3554 * t + 0.4275, -0.0665 * t + 0.0008, -0.0950 * t + 0.0092};
+    const double C[3] = {-0.0227 * t + 5.3251, -0.0004 * t + 0.2125, -0.0079 * t + 0.2102};
+    const double D[3] = {0.1206 * t - 2.5771, -0.0641 * t - 0.8989, -0.0441 * t - 1.6537};
+    const double E[3] = {-0.0670 * t + 0.3703, -0.0033 * t + 0.0452, -0.0109 * t + 0.0529};
+    const double pi = 3.14159265358979323846;
+    const double chi = (4.0 / 9.0 - t / 120.0) * (pi - 2.0 * th);
+    const double th2 = th * th, th3 = th2 * th, t2 = t * t;
+    const double zen[3] = {
+        (4.0453 * t - 4.9710) * std::tan(chi) - 0.2155 * t + 2.4192,
+        (0.00165 * th3 - 0.00375 * th2 + 0.00209 * th) * t2 + (-0.02903 * th3 + 0.06377 * th2 - 0.03202 * th + 0.00394) * t +
+            (0.11693 * th3 - 0.21196 * th2 + 0.06052 * th + 0.25886),
+        (0.00275 * th3 - 0.00610 * th2 + 0.00317 * th) * t2 + (-0.04214 * th3 + 0.08970 * th2 - 0.04153 * th + 0.00516) * t +
+            (0.15346 * th3 - 0.26756 * th2 + 0.06670 * th + 0.26688)};
+    const double cs = std::cos(th);
+    for (int k = 0; k < 3; ++k) {
+        co[0][k] = A[k]; co[1][k] = B[k]; co[2][k] = C[k]; co[3][k] = D[k]; co[4][k] = E[k];
+        co[5][k] = zen[k];
+        co[6][k] = (1.0 + A[k] * std::exp(B[k] / 1.0)) * (1.0 + C[k] * std::exp(D[k] * th) + E[k] * cs * cs);
+    }
+    return OCEAN_OK;
+}
+
+// What the kernels read of a sky: the fp32 outputs of ocean_sky_coefficients (what a UBO would carry), with ZenithLum / ZeroThetaSun formed
+// from them in double and rounded once.
+static int sky_dev(const ocean_sky* s, SkyDev& d)
+{
+    ocean_sky_coeffs k;
+    OCEAN_TRY(ocean_sky_coefficients(s, &k));
+    for (int i = 0; i < 3; ++i) {
+        d.sun[i] = k.sun_dir[i];
+        d.A[i] = k.A[i]; d.B[i] = k.B[i]; d.C[i] = k.C[i]; d.D[i] = k.D[i]; d.E[i] = k.E[i];
+        d.zn[i] = (float)((double)k.zenith_lum[i] / (double)k.zero_theta_sun[i]);
+        d.sun_color[i] = s->sun_color[i];
+    }
+    d.sun_intensity = s->sun_intensity;
+    return OCEAN_OK;
+}
+
+// Calls that read no frame: the consumers' stream only orders them among the other consumer calls.
+static void no_frame(const ocean_ctx* c, LastFrame& f)
+{
+    f = LastFrame{};
+    f.set = c->last_set;
+    f.st = stream_of(c, f.set);
+}
+
+static unsigned point_blocks(uint32_t count)
+{
+    return std::min<unsigned>((count + 255u) / 256u, 2048u);      // eight workgroups per compute unit; the kernels stride over the rest
+}
+
+static int sky_args(ocean_ctx* c, const ocean_sky* s, LastFrame& f, SkyArgs& a)
+{
+    if (!c) return OCEAN_E_INVALID;
+    OCEAN_TRY(sky_dev(s, a.sky));
+    no_frame(c, f);
+    return OCEAN_OK;
+}
+
+static int launch_sky(SkyArgs& a, uint32_t count, const void* d_dirs, void* d_out, void*, hipStream_t st)
+{
+    a.dirs = static_cast<const float*>(d_dirs);
+    a.out = static_cast<float4*>(d_out);
+    a.count = count;
+    hipLaunchKernelGGL(k_sky_radiance, dim3(point_blocks(count)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+static int seabed_args(ocean_ctx* c, LastFrame& f, SeabedArgs& a)
+{
+    if (!c) return OCEAN_E_INVALID;
+    no_frame(c, f);
+    return OCEAN_OK;
+}
+
+static int launch_seabed(SeabedArgs& a, uint32_t count, const void* d_xz, void* d_out, void*, hipStream_t st)
+{
+    a.xz = static_cast<const float2*>(d_xz);
+    a.out = static_cast<float4*>(d_out);
+    a.count = count;
+    hipLaunchKernelGGL(k_eval_seabed, dim3(point_blocks(count)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+// Validation of a sky and a water, and everything of the shading kernel's arguments that is uniform over the launch.
+static int shade_args(ocean_ctx* c, const ocean_sky* s, const ocean_water* w, ShadeArgs& a)
+{
+    if (!c || !w) return OCEAN_E_INVALID;
+    OCEAN_TRY(sky_dev(s, a.sky));
+    if (!all_finite(w->cam_pos, 3) || !std::isfinite(w->height) || !all_finite(w->absorb, 3) || !all_finite(w->scatter, 3) ||
+        !all_finite(w->backscatter, 3) || !all_finite(w->terrain_color, 3) || !std::isfinite(w->sky_intensity) ||
+        !std::isfinite(w->specular_intensity) || !std::isfinite(w->specular_highlights) || !std::isfinite(w->seabed_factor))
+        return OCEAN_E_INVALID;
+    if (!(w->specular_highlights > 0.0f) || w->fresnel > (uint32_t)OCEAN_FRESNEL_PHYSICAL || w->seabed > (uint32_t)OCEAN_SEABED_FLAT) return OCEAN_E_INVALID;
+    for (int k = 0; k < 3; ++k) {
+        if (!(w->absorb[k] > 0.0f)) return OCEAN_E_INVALID;
+        a.cam[k] = w->cam_pos[k];
+        a.absorb01[k] = (float)((double)w->absorb[k] * 0.1);
+        a.scatter01[k] = (float)((double)w->scatter[k] * 0.1);
+        a.df0[k] = (float)((0.33 * (double)w->backscatter[k]) / (double)w->absorb[k]);
+        a.terrain[k] = w->terrain_color[k];
+    }
+    a.height = w->height;
+    a.sky_intensity = w->sky_intensity; a.specular_intensity = w->specular_intensity; a.highlights = w->specular_highlights;
+    a.seabed_factor = w->seabed_factor;
+    const double at0 = (1.33477 - 1.0) / (1.33477 + 1.0);
+    a.f0 = (float)(at0 * at0);
+    a.physical_fresnel = w->fresnel == (uint32_t)OCEAN_FRESNEL_PHYSICAL;
+    a.foam_white = w->foam_white != 0; a.tonemap = w->tonemap != 0;
+    return OCEAN_OK;
+}
+
+static int launch_shade(ShadeArgs& a, bool reference_seabed, uint32_t count, const void* d_pos, const void* d_nrm,
+                        void* d_rgba, void* d_aux, hipStream_t st)
+{
+    a.pos = static_cast<const float4*>(d_pos);
+    a.nrm = static_cast<const float4*>(d_nrm);
+    a.out_rgba = static_cast<float4*>(d_rgba);
+    a.out_aux = static_cast<float4*>(d_aux);
+    a.count = count;
+    if (reference_seabed) hipLaunchKernelGGL(k_shade_points<true>, dim3(point_blocks(count)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_shade_points<false>, dim3(point_blocks(count)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return OCEAN_OK;
+}
+
+extern "C" {
+
+void ocean_default_sky(ocean_sky* s)
+{
+    if (!s) return;
+    s->sun_dir[0] = 0.0f; s->sun_dir[1] = 0.5f; s->sun_dir[2] = 0.866f;      // WaterSurface.h:119
+    s->turbidity = 2.5f;                                                      // SkyPreetham.h:15
+    s->sun_color[0] = s->sun_color[1] = s->sun_color[2] = 1.0f;               // SkyModel.h:26-27
+    s->sun_intensity = 1.0f;
+}
+
+void ocean_default_water(ocean_water* w)
+{
+    if (!w) return;
+    const double absorb[3] = {0.420, 0.063, 0.019}, nm[3] = {680.0, 550.0, 440.0}, terrain[3] = {0.964, 1.0, 0.824};   // WaterSurfaceMesh.h:260-275,303,339,362-383
+    w->cam_pos[0] = 0.0f; w->cam_pos[1] = 60.0f; w->cam_pos[2] = 0.0f;
+    w->height = 50.0f;
+    for (int k = 0; k < 3; ++k) {
+        w->absorb[k] = (float)absorb[k];
+        w->scatter[k] = (float)(0.037 * ((-0.00113 * nm[k] + 1.62517) / (-0.00113 * 514.0 + 1.62517)));
+        w->backscatter[k] = (float)(0.01829 * (double)w->scatter[k] + 0.00006);
+        w->terrain_color[k] = (float)terrain[k];
+    }
+    w->sky_intensity = 1.0f; w->specular_intensity = 1.0f; w->specular_highlights = 32.0f;
+    w->fresnel = OCEAN_FRESNEL_REFERENCE; w->seabed = OCEAN_SEABED_REFERENCE;
+    w->seabed_factor = 0.75f;
+    w->foam_white = 1; w->tonemap = 1;
+}
+
+int ocean_sky_coefficients(const ocean_sky* s, ocean_sky_coeffs* out)
+{
+    if (!out) return OCEAN_E_INVALID;
+    double sun[3], co[7][3];
+    OCEAN_TRY(sky_double(s, sun, co));
+    float* rows[7] = {out->A, out->B, out->C, out->D, out->E, out->zenith_lum, out->zero_theta_sun};
+    for (int k = 0; k < 3; ++k) out->sun_dir[k] = (float)sun[k];
+    out->turbidity = s->turbidity;
+    for (int r = 0; r < 7; ++r) {
+        for (int k = 0; k < 3; ++k) rows[r][k] = (float)co[r][k];
+        rows[r][3] = 0.0f;
+    }
+    return OCEAN_OK;
+}
+
+int ocean_sky_radiance(ocean_t* c, const ocean_sky* s, const float* dirs, uint32_t count, float* out)
+{
+    LastFrame f;
+    SkyArgs a;
+    return staged_call(c, sky_args(c, s, f, a), f, a, launch_sky, count, dirs, 3, out, nullptr, 1);
+}
+
+int ocean_sky_radiance_device(ocean_t* c, const ocean_sky* s, const void* d_dirs, uint32_t count, void* d_out)
+{
+    LastFrame f;
+    SkyArgs a;
+    return device_call(c, sky_args(c, s, f, a), f, a, launch_sky, count, d_dirs, d_out, nullptr, 1);
+}
+
+int ocean_eval_seabed(ocean_t* c, const float* xz, uint32_t count, float* out)
+{
+    LastFrame f;
+    SeabedArgs a;
+    return staged_call(c, seabed_args(c, f, a), f, a, launch_seabed, count, xz, 2, out, nullptr, 1);
+}
+
+int ocean_eval_seabed_device(ocean_t* c, const void* d_xz, uint32_t count, void* d_out)
+{
+    LastFrame f;
+    SeabedArgs a;
+    return device_call(c, seabed_args(c, f, a), f, a, launch_seabed, count, d_xz, d_out, nullptr, 1);
+}
+
+int ocean_shade_points_device(ocean_t* c, const ocean_sky* s, const ocean_water* w, const void* d_pos, const void* d_nrm, uint32_t count,
+                              void* d_out_rgba, void* d_out_aux)
+{
+    ShadeArgs a;
+    OCEAN_TRY(call_checks(c, shade_args(c, s, w, a), count, !d_pos || !d_nrm || !d_out_rgba));
+    if (count == 0) return OCEAN_OK;
+    LastFrame f;
+    no_frame(c, f);
+    OCEAN_TRY(consumer_begin(c, f.st));
+    OCEAN_TRY(launch_shade(a, w->seabed == (uint32_t)OCEAN_SEABED_REFERENCE, count, d_pos, d_nrm, d_out_rgba, d_out_aux, f.st));
+    return consumer_end(c, f.st);
+}
+
+// The host form stages [rgba | aux | pos | nrm], float4 rows all, in the context's buffer (the aux rows also where the caller wants none:
+// the layout does not depend on it).
+int ocean_shade_points(ocean_t* c, const ocean_sky* s, const ocean_water* w, const float* pos, const float* nrm, uint32_t count,
+                       float* out_rgba, float* out_aux)
+{
+    ShadeArgs a;
+    OCEAN_TRY(call_checks(c, shade_args(c, s, w, a), count, !pos || !nrm || !out_rgba));
+    if (count == 0) return OCEAN_OK;
+    LastFrame f;
+    no_frame(c, f);
+    const size_t rows = (size_t)count * sizeof(float4), bytes = 4 * rows;
+    if (bytes > c->staging_bytes) OCEAN_TRY(regrow(c, &c->staging, (void**)nullptr, bytes, c->staging_bytes, bytes, [] {}));
+    char* d_rgba = static_cast<char*>(c->staging);
+    char* d_aux = d_rgba + rows;
+    char* d_pos = d_aux + rows;
+    char* d_nrm = d_pos + rows;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    HIP_TRY(hipMemcpyAsync(d_pos, pos, rows, hipMemcpyHostToDevice, f.st));
+    HIP_TRY(hipMemcpyAsync(d_nrm, nrm, rows, hipMemcpyHostToDevice, f.st));
+    OCEAN_TRY(launch_shade(a, w->seabed == (uint32_t)OCEAN_SEABED_REFERENCE, count, d_pos, d_nrm, d_rgba, out_aux ? d_aux : nullptr, f.st));
+    HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, rows, hipMemcpyDeviceToHost, f.st));
+    if (out_aux) HIP_TRY(hipMemcpyAsync(out_aux, d_aux, rows, hipMemcpyDeviceToHost, f.st));
+    OCEAN_TRY(consumer_end(c, f.st));
+    HIP_TRY(hipStreamSynchronize(f.st));
+    return OCEAN_OK;
+}
+
+int ocean_shade_grid(ocean_t* c, const ocean_sky* s, const ocean_water* w)
+{
+    ShadeArgs a;
+    OCEAN_TRY(shade_args(c, s, w, a));
+    if (!c->prepared || !c->grid_fresh || !c->grid_vertices) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t verts = c->grid_vertices;
+    if (verts > c->shaded_capacity)
+        OCEAN_TRY(regrow(c, &c->shaded, (float4**)nullptr, (size_t)verts * sizeof(float4), c->shaded_capacity, verts, [c] { c->shaded_vertices = 0; }));
+    LastFrame f;
+    no_frame(c, f);
+    OCEAN_TRY(consumer_begin(c, f.st));            // behind the vertex stage that wrote the grid, whichever chain's stream it ran on
+    OCEAN_TRY(launch_shade(a, w->seabed == (uint32_t)OCEAN_SEABED_REFERENCE, verts, c->grid_pos, c->grid_nrm, c->shaded, nullptr, f.st));
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->shaded_vertices = verts;
+    return OCEAN_OK;
+}
+
+int ocean_read_shaded(ocean_t* c, float* rgba)
+{
+    if (!c || !rgba) return OCEAN_E_INVALID;
+    if (!c->shaded_vertices) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    HIP_TRY(hipMemcpy(rgba, c->shaded, (size_t)c->shaded_vertices * sizeof(float4), hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+int ocean_device_shaded(ocean_t* c, void** d_rgba, uint32_t* vertices)
+{
+    if (!c) return OCEAN_E_INVALID;
+    if (d_rgba) *d_rgba = c->shaded_vertices ? c->shaded : nullptr;
+    if (vertices) *vertices = c->shaded_vertices;
+    return OCEAN_OK;
 }
 
 }  // extern "C"

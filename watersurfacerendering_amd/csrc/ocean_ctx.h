@@ -239,6 +239,12 @@ struct ocean_ctx {
     unsigned* wave_scratch = nullptr;
     std::vector<uint32_t> wave_count;
     std::vector<float> wave_length;
+    // The grid "as rendered" (ocean_shade_grid): one float4 per vertex of the vertex stage's output, grown to the largest grid seen and
+    // freed by ocean_destroy.  shaded_vertices is 0 while there is no image; grid_fresh says that a grid has been displaced since the last
+    // ocean_prepare (grid_vertices alone survives Prepare: ocean_read_grid may still read the old vertices).
+    float4* shaded = nullptr;
+    uint32_t shaded_vertices = 0, shaded_capacity = 0;
+    bool grid_fresh = false;
     unsigned long long* stamps = nullptr;   // diagnostic builds only
     hipEvent_t start_ev = nullptr;      // ocean_time_frames: start of the timed region
     hipEvent_t end_ev[MAXD] = {};       //                    end of every chain
