@@ -1,7 +1,9 @@
 """numpy restatement of the surface bounds (include/ocean_consumers.h: ocean_build_bounds_tiles, ocean_patch_bounds): the min/max pyramid
 of a displacement map and the patch query, in the fp32 order the header states -- and the inputs the GPU tests run, which
-tests/test_bounds.py vets on the CPU.  TEST INFRASTRUCTURE ONLY (tests/test_bounds.py, tests/test_bounds_tiles_gpu.py,
-tests/test_patch_bounds_gpu.py)."""
+tests/test_bounds.py vets on the CPU: at their defaults the ones for the crafted 16^2 maps (tests/test_patch_bounds_gpu.py), with n = 256
+the ones for a real sea of 256^2 tiles (tests/test_chain_readers_sizes_gpu.py).  The restatement itself is general in the tile size.  TEST
+INFRASTRUCTURE ONLY (tests/test_bounds.py, tests/test_bounds_tiles_gpu.py, tests/test_patch_bounds_gpu.py,
+tests/test_chain_readers_sizes_gpu.py)."""
 import numpy as np
 
 import crafted_maps as CM
@@ -131,30 +133,37 @@ PADS = (0, 1, 4)
 FIRST_LEVELS = (1, 3)
 
 
+NODE_SEED = 20261
+NODES_PER_LEVEL = 64                # of the levels below log2 n - 3, which have more nodes than that
+
+
 def node_rects(grid=CM.GRID, vd=CM.VD, n=N):
-    """Rectangles whose index range on a cascade of uv_scale 1 is exactly ONE node of level l = 1 .. log2 n, for every node of every level:
+    """Rectangles whose index range on a cascade of uv_scale 1 is exactly ONE node of level l = 1 .. log2 n: for every node of the levels
+    from log2 n - 3 on (at most 8 x 8 nodes), and for NODES_PER_LEVEL seeded nodes of each level below (n = 16: every node of every level).
     t(p0) = k 2^l + 0.25 and t(p1) = (k + 1) 2^l - 1.75 give i0 = k 2^l, i1 = (k + 1) 2^l - 1.  On the reference mesh every end is exact.
     Returns (rects [*, 4], level [*], node y [*], node x [*])."""
     out, lv, ny, nx = [], [], [], []
     top = int(n).bit_length() - 1
+    rng = np.random.default_rng(NODE_SEED + n)
     p = lambda t: ((t + 0.5) / n * grid - grid // 2) * vd
     for l in range(1, top + 1):
-        for y in range(n >> l):
-            for x in range(n >> l):
-                out.append((p(x * 2 ** l + 0.25), p(y * 2 ** l + 0.25), p((x + 1) * 2 ** l - 1.75), p((y + 1) * 2 ** l - 1.75)))
-                lv.append(l); ny.append(y); nx.append(x)
+        ext = n >> l
+        nodes = np.arange(ext * ext) if l >= top - 3 else np.sort(rng.choice(ext * ext, NODES_PER_LEVEL, replace=False))
+        for y, x in zip((nodes // ext).tolist(), (nodes % ext).tolist()):
+            out.append((p(x * 2 ** l + 0.25), p(y * 2 ** l + 0.25), p((x + 1) * 2 ** l - 1.75), p((y + 1) * 2 ** l - 1.75)))
+            lv.append(l); ny.append(y); nx.append(x)
     return np.array(out, np.float64).astype(np.float32), np.array(lv), np.array(ny), np.array(nx)
 
 
-def rect_set(grid, vd, count=RECTS, seed=RECT_SEED):
-    """rects [count, 4] over a mesh of width W = grid * vd: random ones of every size from a tenth of a texel of tile 0 to more than the
-    tile, ones aligned to nodes, points (x0 == x1, and z0 == z1), reversed ends, ones spanning more than a tile, and copies shifted by
-    whole mesh periods to negative coordinates."""
+def rect_set(grid, vd, count=RECTS, seed=RECT_SEED, n=N):
+    """rects [count, 4] over a mesh of width W = grid * vd: random ones of every size from a tenth of a texel of tile 0 (n^2 texels) to
+    more than the tile, ones aligned to nodes, points (x0 == x1, and z0 == z1), reversed ends, ones spanning more than a tile, and copies
+    shifted by whole mesh periods to negative coordinates."""
     rng = np.random.default_rng(seed)
     w = abs(grid * vd)
     r = np.empty((count, 4), np.float64)
     centre = rng.uniform(-0.7 * w, 0.7 * w, (count, 2))
-    size = w / N * np.exp2(rng.uniform(-3.3, 4.3, (count, 2)))                  # 0.1 texel .. 1.2 tiles
+    size = w / n * np.exp2(rng.uniform(-3.3, int(n).bit_length() - 1 + 0.3, (count, 2)))    # 0.1 texel .. 1.2 tiles
     r[:, 0:2] = centre - 0.5 * size
     r[:, 2:4] = centre + 0.5 * size
     k = np.arange(count)
@@ -173,7 +182,7 @@ def rect_set(grid, vd, count=RECTS, seed=RECT_SEED):
     far = k % 5 == 4                                                            # whole mesh periods towards negative coordinates
     r[far, 0] -= 3.0 * w; r[far, 2] -= 3.0 * w
     r[far & (k % 2 == 0), 1] -= 5.0 * w; r[far & (k % 2 == 0), 3] -= 5.0 * w
-    aligned = node_rects(grid, vd)[0].astype(np.float64)                        # rows 400 .. 484: every node of every level, as they are
+    aligned = node_rects(grid, vd, n)[0].astype(np.float64)                     # rows 400 .. (n = 16: 484): node_rects, as they are
     r[400:400 + len(aligned)] = aligned
     return r.astype(np.float32)
 
@@ -208,3 +217,72 @@ def cases():
             if pad != PADS[k % len(PADS)]:
                 out.append((tag, first, count, sc, grid, vd, pad, k % 2 == 1))
     return out
+
+
+# ---- what tests/test_chain_readers_sizes_gpu.py runs on a real sea of 256^2 tiles (tests/lod.py: SIZES_N, SIZES_TILES) ----------------------
+# Eight levels: node offsets beyond level 4, levels the builder's second launch writes, w >= N at 256, pads wider than a tile.
+SIZES_RECTS = 2051                  # fills neither the last wave nor the last block; rows 400 .. 740 are node_rects(n = 256)
+SIZES_PADS = (0, 1, 64, 300, 65536)             # none, the vertex stage's, 2^(L+1) of level 5, wider than the tile, the largest accepted
+SIZES_FIRST_LEVELS = (1, 4, 8)                  # all stored, the common culling set, the top alone
+
+
+def sizes_surfaces():
+    """(tag, first_tile, cascades, uv_scales, grid, vertex_distance) on six tiles of crafted_maps.LENGTHS."""
+    sets = ((0, 1, 1.0), (0, 3, 0.37), (2, 3, 2.5), (1, 5, 1.0))
+    out = [(f"tiles {first}..{first + count - 1} base {base}", first, count, CM.scales(first, count, base), CM.GRID, CM.VD) for first, count, base in sets]
+    out.append(("free uv_scales", 0, 3, [1.0, 2.7, 0.37], CM.GRID, CM.VD))
+    out.append(("a negative uv_scale", 0, 3, [1.0, -0.61, 2.2], CM.GRID, CM.VD))
+    out.append(("grid 513, tiles 3..5", 3, 3, CM.scales(3, 3), 513, CM.VD))
+    return out
+
+
+def sizes_cases():
+    """(tag, first_tile, cascades, uv_scales, grid, vertex_distance, pad, with_planes): every surface with the pads in rotation, planes on
+    every other one -- and the second surface with every other pad, planes the other way round."""
+    out = []
+    for k, (tag, first, count, sc, grid, vd) in enumerate(sizes_surfaces()):
+        out.append((tag, first, count, sc, grid, vd, SIZES_PADS[k % len(SIZES_PADS)], k % 2 == 0))
+    tag, first, count, sc, grid, vd = sizes_surfaces()[1]
+    out += [(tag, first, count, sc, grid, vd, pad, True) for pad in SIZES_PADS if pad != SIZES_PADS[1]]
+    return out
+
+
+# The guarantee at a real size, on the device and in numpy (tests/test_bounds.py): rest points inside a rectangle, evaluated forward at mip
+# level L, against the rectangle's box at pad_texels = 2^(L+1) as include/ocean_consumers.h tells such a caller (level 0: pad 0).
+CONTAIN_RECTS, CONTAIN_POINTS, CONTAIN_SEED = 2000, 9, 20263
+CONTAIN_SCALES = (1.0, 2.7, 0.37)               # three cascades from tile 0, free uv_scales
+CONTAIN_LEVELS = (0, 1, 3, 5, 8)
+
+
+def containment_inputs(grid, vd, n):
+    """(rects [CONTAIN_RECTS, 4], xz [CONTAIN_RECTS * CONTAIN_POINTS, 2]): rect_set for tiles of n^2 -- wrapped, negative and reversed ones
+    among them --, and per rectangle its two named corners and seven seeded points between them, clamped to the rectangle in fp32."""
+    rects = rect_set(grid, vd, CONTAIN_RECTS, n=n)
+    assert np.isfinite(rects).all()
+    s = np.random.default_rng(CONTAIN_SEED).uniform(0.0, 1.0, (CONTAIN_RECTS, CONTAIN_POINTS, 2))
+    s[:, 0], s[:, 1] = 0.0, 1.0
+    r = rects.astype(np.float64)
+    x = (r[:, None, 0] + (r[:, 2] - r[:, 0])[:, None] * s[..., 0]).astype(np.float32)
+    z = (r[:, None, 1] + (r[:, 3] - r[:, 1])[:, None] * s[..., 1]).astype(np.float32)
+    x = np.clip(x, np.minimum(rects[:, 0], rects[:, 2])[:, None], np.maximum(rects[:, 0], rects[:, 2])[:, None])
+    z = np.clip(z, np.minimum(rects[:, 1], rects[:, 3])[:, None], np.maximum(rects[:, 1], rects[:, 3])[:, None])
+    return rects, np.stack([x, z], axis=-1).reshape(-1, 2)
+
+
+def containment_query(level):
+    """(footprint, max_level, pad_texels) that put every cascade on `level` with t == 0, and the pad the header prescribes for it."""
+    return (0.0, 0, 0) if level == 0 else (np.inf, level, 2 ** (level + 1))
+
+
+def containment_excess(pos, lo, hi, e):
+    """(largest excess of a position over its rectangle's box on x, y or z; largest lo.w - w) of the positions pos [rects * CONTAIN_POINTS, 4]
+    -- negative: that far inside --, after asserting that every position lies in [lo - e, hi + e] and that its w is at least lo.w - e_w."""
+    p = np.asarray(pos, dtype=np.float64).reshape(len(lo), CONTAIN_POINTS, 4)
+    lo, hi = np.asarray(lo, dtype=np.float64)[:, None], np.asarray(hi, dtype=np.float64)[:, None]
+    assert np.isfinite(p).all() and np.isfinite(lo).all() and np.isfinite(hi[..., :3]).all()
+    over = np.maximum(p[..., :3] - hi[..., :3], lo[..., :3] - p[..., :3])
+    over_w = lo[..., 3] - p[..., 3]
+    bad = (over > e[:3]).any(axis=2) | (over_w > e[3])
+    worst = float(over.max()), float(over_w.max())
+    assert not bad.any(), f"{int(bad.sum())} positions outside their box, the first in rectangle {np.nonzero(bad.any(axis=1))[0][0]}; largest excess {worst[0]:.3e}, of w {worst[1]:.3e}; slack {e.tolist()}"
+    return worst

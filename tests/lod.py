@@ -1,7 +1,9 @@
 """numpy restatement of the LOD sampler (include/ocean_consumers.h: ocean_sample_surface_lod, ocean_displace_grid_lod): the level rule, the
 trilinear sample, the point form and the grid form, in the fp32 order the header states -- and the inputs the GPU tests run, which
-tests/test_lod.py vets on the CPU.  TEST INFRASTRUCTURE ONLY (tests/test_lod.py, tests/test_lod_sampler_gpu.py).  The bilinear sample and
-the mip chain are oracle/consumer.py's, imported and not copied."""
+tests/test_lod.py vets on the CPU: at their defaults the ones for the crafted 16^2 maps (tests/test_lod_sampler_gpu.py), with n = 256 the
+ones for a real sea of 256^2 tiles (tests/test_chain_readers_sizes_gpu.py).  The restatement itself is general in the tile size.  TEST
+INFRASTRUCTURE ONLY (tests/test_lod.py, tests/test_bounds.py, tests/test_lod_sampler_gpu.py, tests/test_chain_readers_sizes_gpu.py).  The
+bilinear sample and the mip chain are oracle/consumer.py's, imported and not copied."""
 import numpy as np
 
 import crafted_maps as CM
@@ -126,13 +128,32 @@ NAN_ROW, INF_ROW = 5, 11            # in every point set with that many rows: a 
 POINT_SEED = 20250
 
 
-def point_set(count, grid, vertex_distance, seed=POINT_SEED):
-    """xzf [count, 3]: uniform rest points over 1.4 mesh widths, footprints cycling through FOOTPRINT_TEXELS."""
+def footprint_texels(n=N):
+    """Footprints in texels of tile 0 at uv_scale 1 for tiles of n^2: 0, negative, both sides of 1, every power of two up to n with one
+    value between each pair, n itself, above n, far above, +inf, a few that are no power of two, and 1e-30.  n = 16: FOOTPRINT_TEXELS."""
+    if n == N:
+        return FOOTPRINT_TEXELS
+    out = [0.0, -1.0, 0.5, 1.0]
+    for k in range(int(n).bit_length() - 1):
+        out += [(1.5 if k % 2 == 0 else 1.375) * 2.0 ** k, 2.0 ** (k + 1)]       # between 2^k and 2^(k+1), then 2^(k+1); the last is n
+    return tuple(out + [1.25 * n, 1.0e6, np.inf, 0.3, 2.5, 7.0, 2.0 / 0.75, 1.0e-30])
+
+
+def point_meshes(n=N):
+    """POINT_MESHES for tiles of n^2: the reference mesh, and n quads of one metre, where texels_per_metre is exactly uv_scale."""
+    return ((CM.GRID, CM.VD), (n, 1.0))
+
+
+def point_set(count, grid, vertex_distance, seed=POINT_SEED, n=N):
+    """xzf [count, 3]: uniform rest points over 1.4 mesh widths, footprints cycling through footprint_texels(n) (in a stride coprime to
+    their number, so that every one is reached)."""
     rng = np.random.default_rng(seed + count)
     width = grid * vertex_distance
+    table = footprint_texels(n)
+    stride = next(s for s in (7, 11, 13) if len(table) % s)
     xzf = np.empty((count, 3), np.float32)
     xzf[:, :2] = rng.uniform(-0.7 * width, 0.7 * width, (count, 2))
-    xzf[:, 2] = (np.array(FOOTPRINT_TEXELS, np.float64) * (width / N))[(np.arange(count) * 7) % len(FOOTPRINT_TEXELS)]
+    xzf[:, 2] = (np.array(table, np.float64) * (width / n))[(np.arange(count) * stride) % len(table)]
     if count > NAN_ROW:
         xzf[NAN_ROW, 2] = np.nan
     if count > INF_ROW:
@@ -145,15 +166,15 @@ def specified_rows(xzf):
     return np.isfinite(xzf[:, 0]) & np.isfinite(xzf[:, 1])
 
 
-def point_cases():
+def point_cases(cascade_sets=CASCADE_SETS, counts=POINT_COUNTS, settings=LOD_SETTINGS, meshes=POINT_MESHES):
     """(first_tile, cascades, uv_base, grid, vertex_distance, points, scale, max_level): every cascade set, uv base, mesh, count and LOD
     setting appears, in a rotation and not the full product."""
     out, k = [], 0
-    for first, count in CASCADE_SETS:
+    for first, count in cascade_sets:
         for base in UV_BASES:
-            for grid, vd in POINT_MESHES:
-                points = POINT_COUNTS[k % len(POINT_COUNTS)]
-                scale, max_level = LOD_SETTINGS[k % len(LOD_SETTINGS)]
+            for grid, vd in meshes:
+                points = counts[k % len(counts)]
+                scale, max_level = settings[k % len(settings)]
                 out.append((first, count, base, grid, vd, points, scale, max_level))
                 k += 1
     return out
@@ -166,3 +187,37 @@ GRID_PLAIN = ((255, 0, 3, 1.0, 1.0, 0), (255, 0, 3, 2.5, 1.0, 0), (255, 3, 3, 0.
               (16, 0, 1, 1.0, 1.0, 0), (255, 0, 8, 0.37, 1.0, 1), (15, 3, 3, 0.37, 0.75, 0))
 GRID_UNDER = ((16, 0, 3, 1.0, 1.0, 0), (15, 0, 8, 2.5, 1.0, 0), (3, 3, 3, 2.5, 1.0, 0), (2, 0, 8, 1.0, 1.0, 0), (1, 0, 3, 1.0, 1.0, 0),
               (255, 0, 8, 2.5, 1.0, 0), (17, 3, 3, 1.0, 1.0, 0), (17, 0, 8, 1.0, 1.0, 1), (16, 0, 3, 2.5, 0.75, 0), (16, 3, 1, 2.0, 1.0, 4))
+
+
+# ---- what tests/test_chain_readers_sizes_gpu.py runs on a real sea of 256^2 tiles (six of them: crafted_maps.LENGTHS[:6]) -------------------
+# A chain of 256^2 has eight levels, the last two written by the builders' second launch; level offsets, `top`, max_level and the exponent
+# of rho all pass the values a 16^2 chain stops at.
+SIZES_N, SIZES_TILES = 256, 6
+SIZES_CASCADE_SETS = ((0, 1), (0, 3), (2, 3), (1, 5))
+SIZES_POINT_COUNTS = (1, 257, 1000)
+SIZES_LOD_SETTINGS = ((1.0, 0), (1.0, 1), (1.0, 5), (1.0, 8), (0.75, 0))      # no limit, one level, inside the chain, log2 N spelled out; scaled
+
+
+def sizes_point_cases():
+    """point_cases() for the 256^2 sea: 24 cases, every pair of (count, LOD setting) among them."""
+    return point_cases(SIZES_CASCADE_SETS, SIZES_POINT_COUNTS, SIZES_LOD_SETTINGS, point_meshes(SIZES_N))
+
+
+# Grids at CM.VD over the 256^2 sea, (grid, first_tile, cascades, uv_base, scale, max_level).  A cascade of uv_scale s on a grid of g quads
+# has rho = scale * s * 256 / g.  PLAIN: rho <= 1 for every cascade (256 quads at uv_scale 1 sit exactly on 1).  UNDER: 255 quads blend
+# level 0 with a little of level 1; 32, 4 and 1 quads at uv_scale 1 sit on levels 3, 6 and the top with t == 0; the sets of several
+# cascades put them on different levels, with blends, one of them cut at max_level 5.
+SIZES_GRID_PLAIN = ((256, 0, 1, 1.0, 1.0, 0), (257, 0, 3, 0.37, 1.0, 0), (300, 2, 3, 0.37, 1.0, 0), (32, 0, 3, 1.0, 1.0e-30, 0))
+SIZES_GRID_UNDER = ((255, 0, 1, 1.0, 1.0, 0), (32, 0, 1, 1.0, 1.0, 0), (4, 0, 1, 1.0, 1.0, 0), (1, 0, 1, 1.0, 1.0, 0),
+                    (32, 0, 3, 1.0, 1.0, 0), (5, 1, 5, 2.5, 1.0, 0), (4, 2, 3, 1.0, 1.0, 5), (3, 0, 3, 1.0, 0.75, 0))
+
+
+def random_maps(n, tiles, seed):
+    """(disp, nrm), each [tiles, n, n, 4] float32, of the CPU tests at sizes beyond crafted_maps: crafted_maps.maps() without its blocks."""
+    rng = np.random.default_rng(seed)
+    disp = rng.standard_normal((tiles, n, n, 4)) * np.array([0.5, 1.0, 0.5, 0.0])
+    disp[..., 3] = rng.uniform(-1.0, 2.0, (tiles, n, n))
+    nrm = np.empty((tiles, n, n, 4))
+    nrm[..., :2] = 0.3 * rng.standard_normal((tiles, n, n, 2))
+    nrm[..., 2:] = 0.02 * rng.standard_normal((tiles, n, n, 2))
+    return disp.astype(np.float32), nrm.astype(np.float32)

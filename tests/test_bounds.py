@@ -195,3 +195,121 @@ def test_every_rest_point_of_a_rectangle_lands_inside_its_box(maps, case, first_
         assert np.all(p[:, :3] <= hi[r, :3] + e[:3]) and np.all(p[:, :3] >= lo[r, :3] - e[:3]), (tag, r, rects[r])
         assert np.all(p[:, 3] >= lo[r, 3] - e[3]), (tag, r)
     print(f"{tag} pad {pad} first_level {first_level}: largest excess over the box {worst:.3e} (slack {e.tolist()})")
+
+
+# ---- the inputs of tests/test_chain_readers_sizes_gpu.py: tiles of 256^2 ---------------------------------------------------------------------
+def test_the_generators_give_the_16_squared_inputs_unchanged_at_their_defaults():
+    """The n parameter's default is the crafted maps' size: the rectangle set of tests/test_patch_bounds_gpu.py is, byte for byte, what the
+    generator gave before it took an n (the digest is of that array), and spelling the default out changes nothing."""
+    import hashlib
+    rects = B.rect_set(CM.GRID, CM.VD)
+    assert hashlib.sha256(rects.tobytes()).hexdigest() == "893517e1c3889052b6ad4280693fa40b1ddcaa1686b05942e3107a874000a72f"
+    assert np.array_equal(B.rect_set(CM.GRID, CM.VD, n=16).view(np.uint32), rects.view(np.uint32))
+    assert all(np.array_equal(a, b) for a, b in zip(B.node_rects(), B.node_rects(n=16)))
+
+
+@pytest.fixture(scope="module")
+def maps256():
+    return L.random_maps(L.SIZES_N, L.SIZES_TILES, 20262)
+
+
+def test_the_256_rectangle_set_has_what_its_docstring_says(maps256):
+    disp, _ = maps256
+    n, top = L.SIZES_N, 8
+    rects, level, ny, nx = B.node_rects(n=n)
+    assert np.bincount(level).tolist() == [0, 64, 64, 64, 64, 64, 16, 4, 1] and np.array_equal(rects.astype(np.float64), B.node_rects(n=n)[0])
+    assert all(len({(y, x) for y, x in zip(ny[level == l], nx[level == l])}) == (level == l).sum() for l in range(1, top + 1))
+    # each is exactly its node: the block's own minimum and maximum, at offsets beyond those of a 16^2 chain
+    lo, hi, seen, _ = B.patch_bounds(disp[:1], [1.0], [1.0], CM.GRID, CM.VD, rects, detail=True)
+    d = seen[0]
+    assert np.array_equal(d["level"], level) and np.array_equal(d["nx0"], nx) and np.array_equal(d["nx1"], nx)
+    assert np.array_equal(d["nz0"], ny) and np.array_equal(d["nz1"], ny) and np.array_equal(d["i0x"], nx << level)
+    for r in range(len(rects)):
+        s = 1 << level[r]
+        block = disp[0][ny[r] * s:(ny[r] + 1) * s, nx[r] * s:(nx[r] + 1) * s].reshape(-1, 4)
+        assert np.array_equal(lo[r, 1::2], block.min(axis=0)[1::2]) and np.array_equal(hi[r, 1], block.max(axis=0)[1]), r
+    r = B.rect_set(CM.GRID, CM.VD, B.SIZES_RECTS, n=n).astype(np.float64)
+    w = CM.GRID * CM.VD
+    assert len(r) == B.SIZES_RECTS and B.SIZES_RECTS % 64 != 0 and B.SIZES_RECTS % 256 != 0 and np.isfinite(r).all()
+    assert np.array_equal(r[400:400 + len(rects)], rects.astype(np.float64)) and 400 + len(rects) < B.SIZES_RECTS
+    size = np.abs(r[:, 2:] - r[:, :2]).max(axis=1) / (w / n)                   # in texels of tile 0
+    assert (size[size > 0] < 0.25).sum() > 10 and all(((size > 2.0 ** k) & (size <= 2.0 ** (k + 1))).sum() > 50 for k in range(0, 8))
+    assert ((size > n) & (size <= 1.25 * n)).sum() > 10 and (size > 1.25 * n).sum() > 100
+    assert (r[:, 0] > r[:, 2]).sum() > 50 and (r[:, 1] > r[:, 3]).sum() > 50 and (np.maximum(r[:, 0], r[:, 2]) < -w).sum() > 50
+
+
+def test_the_256_inputs_reach_every_branch(maps256):
+    """What test_the_gpu_inputs_reach_every_branch asks of the 16^2 inputs, and every level first_level .. 8 for each first_level."""
+    disp, _ = maps256
+    n, top = L.SIZES_N, 8
+    keys = ["one node on x", "two nodes on x", "one node on z", "two nodes on z", "negative index", "w == N - 1", "w == N", "w > N",
+            "first_level clamp", "class 0", "class 1", "class 2", "early stop", "pad beyond a tile", "index beyond 2^16"]
+    reached = dict.fromkeys(keys, 0)
+    pads = set()
+    for first_level in B.SIZES_FIRST_LEVELS:
+        levels = np.zeros(top + 1, np.int64)
+        for tag, first, count, sc, grid, vd, pad, with_planes in B.sizes_cases():
+            sl = slice(first, first + count)
+            rects = B.rect_set(grid, vd, B.SIZES_RECTS, n=n)
+            planes = B.planes_for(grid, vd) if with_planes else None
+            lo, hi, seen, stop = B.patch_bounds(disp[sl], CM.CPU_AMPS[sl], sc, grid, vd, rects, first_level, pad, planes, detail=True)
+            assert np.isfinite(lo).all() and np.isfinite(hi).all() and np.all(lo[:, :3] <= hi[:, :3]), tag
+            pads.add(pad)
+            plain = B.patch_bounds(disp[sl], CM.CPU_AMPS[sl], sc, grid, vd, rects, 1, pad)[0] if first_level > 1 else None
+            for d in seen:
+                inside = ~d["whole"]
+                levels += np.bincount(d["level"][inside], minlength=top + 1)
+                reached["one node on x"] += int((inside & (d["nx0"] == d["nx1"])).sum())
+                reached["two nodes on x"] += int((inside & (d["nx0"] != d["nx1"])).sum())
+                reached["one node on z"] += int((inside & (d["nz0"] == d["nz1"])).sum())
+                reached["two nodes on z"] += int((inside & (d["nz0"] != d["nz1"])).sum())
+                reached["negative index"] += int((inside & ((d["i0x"] < 0) | (d["i0z"] < 0))).sum())
+                reached["w == N - 1"] += int((d["w"] == n - 1).sum())
+                reached["w == N"] += int((d["w"] == n).sum())
+                reached["w > N"] += int((d["w"] > n).sum())
+                reached["pad beyond a tile"] += int(pad >= n)
+                reached["index beyond 2^16"] += int((np.abs(d["i0x"]) > 65536).sum())
+                assert np.all(d["level"] >= first_level) and np.all(d["level"] <= top)
+                assert np.all((d["i1x"] - d["i0x"] + 1 <= (1 << d["level"])) | d["whole"])
+            if plain is not None:
+                reached["first_level clamp"] += int((plain != lo).any(axis=1).sum())
+                assert np.all(lo[:, :3] <= plain[:, :3])
+            if with_planes:
+                for k in (0, 1, 2):
+                    reached[f"class {k}"] += int((hi[:, 3] == k).sum())
+                for k in range(len(planes) - 1):
+                    later = np.zeros(len(rects), bool)
+                    for j in range(k + 1, len(planes)):
+                        later |= B.classify(lo, hi, planes[j:j + 1]) == 1
+                    reached["early stop"] += int(((stop == k) & later).sum())
+            else:
+                assert np.all(hi[:, 3] == 1)
+        # (the whole-tile node a rule gives, not one forced by w >= N: level 8 is reached by w in 129 .. 255 too)
+        assert np.all(levels[first_level:] > 0) and np.all(levels[:first_level] == 0), (first_level, levels)
+    assert all(v > 0 for v in reached.values()), reached
+    assert pads == set(B.SIZES_PADS) and {c[7] for c in B.sizes_cases() if c[6] == 0} == {True, False}
+    assert all(c[1] + c[2] <= L.SIZES_TILES for c in B.sizes_cases())
+
+
+def test_forward_evaluations_at_mip_level_L_stay_inside_the_box_padded_by_two_to_the_L_plus_one(maps256):
+    """include/ocean_consumers.h: a caller "who samples at mip level L sets pad_texels = 2^(L+1)".  With s = u N - 0.5 the level-0
+    texel coordinate, the level-L sample reads the two level-L texels j, j + 1 with j = floor((s + 0.5) / 2^L - 0.5), whose blocks are the
+    level-0 texels j 2^L .. (j + 2) 2^L - 1: from less than 1.5 * 2^L below s to less than 1.5 * 2^L above it, inside floor(s) - pad ..
+    floor(s) + 1 + pad.  A mip texel is a mean formed by monotone rounding and lies between its block's extremes, and t == 0 adds no blend:
+    B.slack as it stands.  The same check runs on the device in tests/test_chain_readers_sizes_gpu.py."""
+    disp, nrm = maps256
+    n, sc, amps = L.SIZES_N, list(B.CONTAIN_SCALES), CM.CPU_AMPS[:3]
+    rects, xz = B.containment_inputs(CM.GRID, CM.VD, n)
+    assert len(rects) == 2000 and len(xz) == 18000
+    e = B.slack(disp[:3], amps)
+    for level in B.CONTAIN_LEVELS:
+        f, max_level, pad = B.containment_query(level)
+        xzf = np.concatenate([xz, np.full((len(xz), 1), f, np.float32)], axis=1)
+        pos, out_nrm, seen = L.sample_surface_lod(disp[:3], nrm[:3], amps, sc, CM.GRID, CM.VD, L.CHOPPY, xzf, 1.0, max_level, detail=True)
+        assert all(np.all(lev == level) and np.all(t == 0) for lev, t in seen)
+        lo, hi = B.patch_bounds(disp[:3], amps, sc, CM.GRID, CM.VD, rects, 1, pad)
+        worst, worst_w = B.containment_excess(pos, lo, hi, e)
+        print(f"level {level} pad {pad}: largest excess over a box {worst:.3e}, of w below its bound {worst_w:.3e} (slack {e.tolist()})")
+    # the check sees a box that is not the rectangle's own: its neighbour's in the list
+    with pytest.raises(AssertionError):
+        B.containment_excess(pos, np.roll(lo, 1, axis=0), np.roll(hi, 1, axis=0), e)

@@ -141,3 +141,95 @@ def test_the_gpu_grid_inputs_are_what_their_lists_say(maps):
                 reached["t > 0"] += int(t[0] > 0)
                 reached["top clamp"] += int(lev[0] == lmax)
     assert all(v > 0 for v in reached.values()), reached
+
+
+# ---- the inputs of tests/test_chain_readers_sizes_gpu.py: tiles of 256^2 ---------------------------------------------------------------------
+def test_the_generators_give_the_16_squared_inputs_unchanged_at_their_defaults():
+    """The n parameter's default is the crafted maps' size: the point set of tests/test_lod_sampler_gpu.py is, byte for byte, what the
+    generator gave before it took an n (the digest is of that array), and spelling the default out changes nothing."""
+    import hashlib
+    xzf = L.point_set(1000, CM.GRID, CM.VD)
+    assert hashlib.sha256(xzf.tobytes()).hexdigest() == "d8c03c9c99f94d0839cc45ef4db7279f6d353788aa7f28da326490d8f2bebd75"
+    assert np.array_equal(L.point_set(1000, CM.GRID, CM.VD, n=16).view(np.uint32), xzf.view(np.uint32))
+    assert L.footprint_texels() is L.FOOTPRINT_TEXELS and L.point_meshes() == L.POINT_MESHES
+    assert L.point_cases() == L.point_cases(L.CASCADE_SETS, L.POINT_COUNTS, L.LOD_SETTINGS, L.POINT_MESHES) and len(L.point_cases()) == 36
+
+
+def test_the_256_footprints_are_what_the_list_says():
+    f = L.footprint_texels(256)
+    powers = [2.0 ** k for k in range(0, 9)]
+    assert set(powers) <= set(f) and all(any(a < x < b for x in f) for a, b in zip(powers, powers[1:]))
+    assert {0.0, -1.0, 0.5, 1.0e-30, np.inf} <= set(f) and any(256 < x < np.inf for x in f) and any(0 < x < 1 for x in f)
+    xzf = L.point_set(257, CM.GRID, CM.VD, n=256)
+    assert np.isnan(xzf[L.NAN_ROW, 2]) and np.isinf(xzf[L.INF_ROW, 0]) and (~L.specified_rows(xzf)).sum() == 1
+    # every footprint of the table is reached by a count that is at least its length
+    want = np.array(f, np.float64) * (CM.GRID * CM.VD / 256)
+    assert {float(x) for x in xzf[np.isfinite(xzf[:, 2]), 2]} == {float(np.float32(x)) for x in want if np.isfinite(x)}
+
+
+@pytest.fixture(scope="module")
+def maps256():
+    return L.random_maps(L.SIZES_N, L.SIZES_TILES, 20262)
+
+
+def test_the_256_point_inputs_reach_every_level_and_every_expected_value_is_finite(maps256):
+    """Every level 0 .. 8 occurs as lev with t == 0, every level 0 .. 7 with t != 0 (on the last level t is 0 by the rule), beside the
+    branches the 16^2 inputs are vetted for."""
+    disp, nrm = maps256
+    n, top = L.SIZES_N, 8
+    flat, blend = np.zeros(top + 1, np.int64), np.zeros(top + 1, np.int64)
+    reached = {"t == 0 inside": 0, "top clamp": 0, "max_level clamp": 0, "nan": 0, "upper level 1x1": 0}
+    cases = L.sizes_point_cases()
+    for first, count, base, grid, vd, points, scale, max_level in cases:
+        sl = slice(first, first + count)
+        xzf = L.point_set(points, grid, vd, n=n)
+        pos, out_nrm, seen = L.sample_surface_lod(disp[sl], nrm[sl], CM.CPU_AMPS[sl], CM.scales(first, count, base), grid, vd, L.CHOPPY, xzf,
+                                                  scale, max_level, detail=True)
+        keep = L.specified_rows(xzf)
+        assert np.isfinite(pos[keep]).all() and np.isfinite(out_nrm[keep]).all(), (first, count, base, grid)
+        lmax = L.lmax_of(n, max_level)
+        rho_nan = np.isnan(xzf[:, 2])
+        for lev, t in seen:
+            ok = keep & ~rho_nan
+            flat += np.bincount(lev[ok & (t == 0)], minlength=top + 1)
+            blend += np.bincount(lev[ok & (t != 0)], minlength=top + 1)
+            reached["t == 0 inside"] += int(((lev > 0) & (lev < lmax) & (t == 0) & keep).sum())
+            reached["top clamp"] += int(((lev == top) & keep).sum())
+            reached["max_level clamp"] += int(((lev == lmax) & (lmax < top) & keep).sum())
+            reached["nan"] += int((rho_nan & (lev == 0) & (t == 0)).sum())
+            reached["upper level 1x1"] += int(((lev == top - 1) & (t > 0) & keep).sum())
+            assert np.all(lev <= lmax) and np.all(t >= 0) and np.all(t < 1)
+        assert np.all(out_nrm[keep, 3] >= 0) and np.all(out_nrm[keep, 3] <= lmax)
+    assert np.all(flat > 0) and np.all(blend[:top] > 0) and blend[top] == 0, (flat, blend)
+    assert all(v > 0 for v in reached.values()), reached
+    assert {(c[0], c[1]) for c in cases} == set(L.SIZES_CASCADE_SETS) and {c[2] for c in cases} == set(L.UV_BASES)
+    assert {(c[5], c[6], c[7]) for c in cases} == {(p, s, m) for p in L.SIZES_POINT_COUNTS for s, m in L.SIZES_LOD_SETTINGS}
+    assert all(first + count <= L.SIZES_TILES for first, count in L.SIZES_CASCADE_SETS)
+
+
+def test_the_256_grid_inputs_are_what_their_lists_say(maps256):
+    disp, nrm = maps256
+    n, top = L.SIZES_N, 8
+    lone, mixed = set(), 0
+    for plain, cases in ((True, L.SIZES_GRID_PLAIN), (False, L.SIZES_GRID_UNDER)):
+        for grid, first, count, base, scale, max_level in cases:
+            sl = slice(first, first + count)
+            sc = CM.scales(first, count, base)
+            assert (max(scale * s * n / grid for s in sc) <= 1.0) == plain, (grid, first, count, base)
+            got_pos, got_nrm, seen = L.displace_grid_lod(disp[sl], nrm[sl], CM.CPU_AMPS[sl], sc, grid, CM.VD, L.CHOPPY, scale, max_level, detail=True)
+            got = CM.bits(got_pos, got_nrm)
+            assert np.isfinite(got_pos).all() and np.isfinite(got_nrm).all() and np.all(got_nrm[:, 3] == 0)
+            flat = CM.bits(*O.displace_grid_cascades(disp[sl], nrm[sl], CM.CPU_AMPS[sl], sc, grid, CM.VD, L.CHOPPY))
+            differ = (got != flat).any(axis=1)
+            if plain:
+                assert all(np.all(lev == 0) and np.all(t == 0) for lev, t in seen) and not differ.any(), (grid, first, count, base)
+            else:
+                assert differ.sum() > len(differ) / 2, (grid, first, count, base, int(differ.sum()), len(differ))
+            levels = [(int(lev[0]), float(t[0])) for lev, t in seen]
+            assert all(np.all(lev == lev[0]) and np.all(t == t[0]) for lev, t in seen)          # one footprint: one level per cascade
+            assert all(l <= L.lmax_of(n, max_level) for l, _ in levels)
+            if count == 1:
+                lone.add(levels[0])
+            mixed += int(len({l for l, _ in levels}) > 1 and any(t > 0 for _, t in levels))
+    assert {(3, 0.0), (6, 0.0), (top, 0.0)} <= lone and any(l == 0 and t > 0 for l, t in lone), lone
+    assert mixed >= 2
