@@ -102,6 +102,27 @@ def test_displace_grid_lod_is_the_restatement_where_cascades_are_undersampled(se
     assert np.all(got[:, 7] == 0)           # normals.w = 0.0f
 
 
+@pytest.mark.parametrize("grid", CM.VERTEX_GRIDS)
+def test_the_point_form_at_the_grid_s_rest_points_is_the_cascade_vertex_stage(sea, grid):
+    """The two forms that share the cascade sum, held to each other: the point form at footprint 0 on the rest points of the grid the
+    vertex stage builds, against ocean_displace_grid_cascades -- words 0 .. 6 of every row, and word 7 = 0 on both sides.  The bits
+    match because VD = 125 / 64: xi * VD is exact and x / VD gives xi back, so the point form's (x / vd + half) / grid is the vertex
+    stage's (float)(xi + half) / (float)grid, and footprint 0 stays on level 0.  No row is left out."""
+    side, half = grid + 1, grid // 2
+    i = np.arange(side * side)
+    vd = np.float32(CM.VD)
+    xzf = np.stack([(i % side - half).astype(np.float32) * vd, (i // side - half).astype(np.float32) * vd,
+                    np.zeros(side * side, np.float32)], axis=1)
+    for first, count in CM.VERTEX_CASCADE_SETS:
+        for base in CM.VERTEX_UV_SCALES:
+            sc = CM.scales(first, count, base)
+            points = CM.bits(*sea.b.sample_surface_lod(xzf, first, sc, grid, CM.VD, CM.VERTEX_CHOPPY))
+            vertices = CM.bits(*sea.b.displace_grid_cascades(sc, first, grid, CM.VD, CM.VERTEX_CHOPPY))
+            assert points.shape == vertices.shape == (side * side, 8)
+            CM.assert_same_bits(points[:, :7], vertices[:, :7], f"grid {grid} tiles {first}..{first + count - 1} uv base {base}")
+            assert not points[:, 7].any() and not vertices[:, 7].any()
+
+
 def _surface(b, first, scales, grid=CM.GRID, vd=CM.VD, iterations=0):
     return b._surface(first, scales, grid, vd, L.CHOPPY, iterations)
 

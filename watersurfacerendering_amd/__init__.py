@@ -584,15 +584,19 @@ class OceanBatch:
         """Mip chain of both maps of `tile` (ocean_build_mips: the reference's s_kUseMipMapping path, Texture2D.cpp:228-330):
         returns (disp_levels, nrm_levels), lists of (N >> l, N >> l, 4) float32 arrays for l = 1 .. log2 N."""
         _abi.check(self._L.ocean_build_mips(self._h, tile), "ocean_build_mips")
-        texels = int(self._L.ocean_mip_texels(self.tile_size))
-        d = np.empty((texels, 4), dtype=np.float32)
-        q = np.empty_like(d)
-        _abi.check(self._L.ocean_read_mips(self._h, d.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p)), "ocean_read_mips")
-        out_d, out_q, off, w = [], [], 0, self.tile_size // 2
+        return self._read_chains("ocean_read_mips")
+
+    def _read_chains(self, call: str, *tile):
+        """The two packed chains `call` (an ocean_read_* of the C ABI, with its arguments between the context and the two pointers)
+        copies out, each split into its levels: two lists of (N >> l, N >> l, 4) float32 arrays for l = 1 .. log2 N."""
+        a = np.empty((int(self._L.ocean_mip_texels(self.tile_size)), 4), dtype=np.float32)
+        b = np.empty_like(a)
+        _abi.check(getattr(self._L, call)(self._h, *tile, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)), call)
+        out_a, out_b, off, w = [], [], 0, self.tile_size // 2
         while w >= 1:
-            out_d.append(d[off:off + w * w].reshape(w, w, 4)); out_q.append(q[off:off + w * w].reshape(w, w, 4))
+            out_a.append(a[off:off + w * w].reshape(w, w, 4)); out_b.append(b[off:off + w * w].reshape(w, w, 4))
             off += w * w; w //= 2
-        return out_d, out_q
+        return out_a, out_b
 
     # -- LOD sampling (include/ocean_consumers.h: ocean_build_mips_tiles, ocean_sample_surface_lod, ocean_displace_grid_lod) -----
     def build_mips_tiles(self, first_tile: int = 0, count: Optional[int] = None):
@@ -603,16 +607,7 @@ class OceanBatch:
 
     def read_mips_tile(self, tile: int):
         """One tile's chains of the set (ocean_read_mips_tile; synchronises): (disp_levels, nrm_levels) as build_mips returns them."""
-        texels = int(self._L.ocean_mip_texels(self.tile_size))
-        d = np.empty((texels, 4), dtype=np.float32)
-        q = np.empty_like(d)
-        _abi.check(self._L.ocean_read_mips_tile(self._h, int(tile), d.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p)),
-                   "ocean_read_mips_tile")
-        out_d, out_q, off, w = [], [], 0, self.tile_size // 2
-        while w >= 1:
-            out_d.append(d[off:off + w * w].reshape(w, w, 4)); out_q.append(q[off:off + w * w].reshape(w, w, 4))
-            off += w * w; w //= 2
-        return out_d, out_q
+        return self._read_chains("ocean_read_mips_tile", int(tile))
 
     def device_mips_tiles(self):
         """(d_disp_mips, d_nrm_mips, first_tile, count, levels) of the set (ocean_device_mips_tiles); the pointers are None without one."""
@@ -679,16 +674,7 @@ class OceanBatch:
     def read_bounds_tile(self, tile: int):
         """One tile's chains of the set (ocean_read_bounds_tile; synchronises): a list of (lo, hi) per level l = 1 .. log2 N, each
         (N >> l, N >> l, 4) float32.  Levels below the set's first_level hold nothing that is specified."""
-        texels = int(self._L.ocean_mip_texels(self.tile_size))
-        lo = np.empty((texels, 4), dtype=np.float32)
-        hi = np.empty_like(lo)
-        _abi.check(self._L.ocean_read_bounds_tile(self._h, int(tile), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)),
-                   "ocean_read_bounds_tile")
-        out, off, w = [], 0, self.tile_size // 2
-        while w >= 1:
-            out.append((lo[off:off + w * w].reshape(w, w, 4), hi[off:off + w * w].reshape(w, w, 4)))
-            off += w * w; w //= 2
-        return out
+        return list(zip(*self._read_chains("ocean_read_bounds_tile", int(tile))))
 
     def device_bounds_tiles(self):
         """(d_lo, d_hi, first_tile, count, levels, first_level) of the set (ocean_device_bounds_tiles); the pointers are None without one."""

@@ -695,8 +695,8 @@ int ocean_prepare(ocean_t* c, uint64_t seed, const float* xi_or_null)
     c->seed = seed;
     c->prepared = true;
     c->have_frame = false;
-    c->lod_ready = false;                       // (the mip set of ocean_build_mips_tiles belongs to a frame of the old spectrum)
-    c->bnd_ready = false;                       // (the bounds set of ocean_build_bounds_tiles likewise)
+    c->lod.ready = false;                       // (the mip set of ocean_build_mips_tiles belongs to a frame of the old spectrum)
+    c->bnd.ready = false;                       // (the bounds set of ocean_build_bounds_tiles likewise)
     c->wave_count.assign(t, 0u);                // (the wave sets were lists of the old spectrum's bins)
     c->grid_fresh = false;                      // (ocean_shade_grid shades only a grid displaced from this spectrum's frames)
     c->shaded_vertices = 0;

@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(256) k_bounds_tiles(const BoundsTilesArgs m)
 // reads inside the chains and writes its own row only.
 // ============================================================================
 struct PatchArgs {
-    QueryArgs q;                       // the surface (q.disp / nrm / xz / iterations / choppy / gain unused; minmax gives A_c)
+    QueryArgs q;                       // the surface (q.s.disp / nrm, q.xz / iterations / choppy / gain unused; q.s.minmax gives A_c)
     const float4* lo;                  // chains of the FIRST tile of the cascade set (tile c at + c * chain_texels)
     const float4* hi;
     const float* rects;                // [count][4] x0, z0, x1, z1
@@ -163,14 +163,14 @@ __global__ void __launch_bounds__(256) k_patch_bounds(const PatchArgs p)
     const float* in = p.rects + (size_t)i * 4;
     const float x0 = in[0], z0 = in[1], x1 = in[2], z1 = in[3];
     const bool finite = isfinite(x0) && isfinite(z0) && isfinite(x1) && isfinite(z1);
-    const float u0 = (x0 / a.vertex_distance + a.half) / a.grid, v0 = (z0 / a.vertex_distance + a.half) / a.grid;
-    const float u1 = (x1 / a.vertex_distance + a.half) / a.grid, v1 = (z1 / a.vertex_distance + a.half) / a.grid;
-    const float fn = (float)a.n;
+    const float u0 = rest_uv(a, x0), v0 = rest_uv(a, z0);
+    const float u1 = rest_uv(a, x1), v1 = rest_uv(a, z1);
+    const float fn = (float)a.s.n;
     float lx = 0.0f, ly = 0.0f, lz = 0.0f, lw = 3.402823466e+38f;
     float hx = 0.0f, hy = 0.0f, hz = 0.0f;
-    for (int c = 0; c < a.count; ++c) {
-        const float sc = a.uv_scale[c];
-        const float amp = fmaxf(fabsf(key_float(a.minmax[2 * c + 0])), fabsf(key_float(a.minmax[2 * c + 1])));
+    for (int c = 0; c < a.s.count; ++c) {
+        const float sc = a.s.uv_scale[c];
+        const float amp = height_amplitude(a.s.minmax, c);
         const float tx0 = u0 * sc * fn - 0.5f, tx1 = u1 * sc * fn - 0.5f;
         const float tz0 = v0 * sc * fn - 0.5f, tz1 = v1 * sc * fn - 0.5f;
         const long long i0x = (long long)(int)floorf(fminf(tx0, tx1)) - p.pad, i1x = (long long)(int)floorf(fmaxf(tx0, tx1)) + 1 + p.pad;
@@ -178,17 +178,17 @@ __global__ void __launch_bounds__(256) k_patch_bounds(const PatchArgs p)
         const long long wx = i1x - i0x, wz = i1z - i0z;
         const long long w = (wx > wz ? wx : wz) + 1;
         int l = p.top;
-        if (finite && w < (long long)a.n) {
+        if (finite && w < (long long)a.s.n) {
             l = 1;
             while ((1ll << l) < w) ++l;
             if (l < p.first_level) l = p.first_level;
         }
-        const int ext = a.n >> l;
+        const int ext = a.s.n >> l;
         const long long mask = ext - 1;
         const int nx0 = (int)((i0x >> l) & mask), nx1 = (int)((i1x >> l) & mask);
         const int nz0 = (int)((i0z >> l) & mask), nz1 = (int)((i1z >> l) & mask);
-        const float4* lo = lod_level_ptr(nullptr, p.lo + (size_t)c * p.chain_texels, a.n, l);
-        const float4* hi = lod_level_ptr(nullptr, p.hi + (size_t)c * p.chain_texels, a.n, l);
+        const float4* lo = lod_level_ptr(nullptr, p.lo + (size_t)c * p.chain_texels, a.s.n, l);
+        const float4* hi = lod_level_ptr(nullptr, p.hi + (size_t)c * p.chain_texels, a.s.n, l);
         const unsigned n00 = (unsigned)(nz0 * ext + nx0), n10 = (unsigned)(nz0 * ext + nx1);
         const unsigned n01 = (unsigned)(nz1 * ext + nx0), n11 = (unsigned)(nz1 * ext + nx1);
         const float4 lo_c = min4(min4(lo[n00], lo[n10]), min4(lo[n01], lo[n11]));

@@ -41,9 +41,9 @@ __global__ void __launch_bounds__(256) k_buoyancy_bodies(const BuoyancyArgs b)
     const unsigned body = blockIdx.x * BUOYANCY_BODIES_PER_BLOCK + (threadIdx.x >> 6);
     if (body >= b.count) return;
     float amp[OCEAN_MAX_CASCADES];
-    query_amplitudes(a, amp);
+    cascade_amplitudes(a.s.minmax, a.s.count, amp);
     float tamp[OCEAN_MAX_CASCADES];
-    if constexpr (FLOW) twin_amplitudes(a, b.tw, tamp);
+    if constexpr (FLOW) cascade_amplitudes(b.tw.minmax, a.s.count, tamp);
 
     const float* w = b.bodies + (size_t)body * 16;
     const float posx = w[0], posy = w[1], posz = w[2];

@@ -1,6 +1,6 @@
 // ocean_consumer_kernels.h -- the kernels behind include/ocean_consumers.h, compiled into ocean_consumers.hip only: the vertex stage and its
-// cascades, the mip chain, the surface query and the ray cast.  The persistent foam's are in ocean_foam_kernels.h,
-// which builds on the query's; the Prepare and pack kernels in ocean_aux_kernels.h; the frame kernels themselves in ocean_kernels.h.
+// cascades, the mip chain, the surface query and the ray cast -- and what every consumer of the maps shares: CascadeSet,
+// height_amplitude, rest_uv, cascade_sum, vertex_normal.  Foam: ocean_foam_kernels.h; LOD: ocean_lod_kernels.h; frames: ocean_kernels.h.
 #pragma once
 #include "ocean_kernels.h"
 
@@ -16,18 +16,65 @@ namespace ocean {
 // fp32 in the order written below (no contraction), which oracle/consumer.py repeats.
 // One thread per vertex; memory-bound (8 texel reads that mostly hit in cache, 2 writes).
 // ============================================================================
-struct GridArgs {
-    const float4* disp;      // [N][N] of the tile
+constexpr int OCEAN_MAX_CASCADES = 8;
+
+// What every consumer reads of a cascade set: the consecutive tiles first .. first + count - 1 of one frame (a single tile: count = 1).
+struct CascadeSet {
+    const float4* disp;      // [N][N] maps of the FIRST tile of the set (tile c at + c * tile_texels)
     const float4* nrm;
-    const unsigned* minmax;  // keys of the tile's raw height range (A = max(|min|, |max|) = WSHeightAmp)
+    const unsigned* minmax;  // keys of the first tile's raw height range, 2 per tile (A = max(|min|, |max|) = WSHeightAmp)
+    size_t tile_texels;      // N * N
+    int n;                   // map size
+    int count;               // cascades, 1 .. OCEAN_MAX_CASCADES
+    float uv_scale[OCEAN_MAX_CASCADES];    // ubo.scale of every cascade, 0 beyond count
+};
+
+// The vertex stage's arguments: the set and the grid it fills.
+struct CascadeArgs {
+    CascadeSet s;
     float4* positions;       // [(g+1)^2]  xyz = displaced position, w = displacement.w (jacobian slot)
     float4* normals;         // [(g+1)^2]  xyz = unit normal, w = 0
-    int n;                   // map size
     int grid;                // quads per side (kTileSize of CreateGridVertices)
     float vertex_distance;   // kScale
-    float uv_scale;          // ubo.scale
     float choppy;            // ubo.WSChoppy = GetDisplacementLambda()
 };
+struct GridArgs : CascadeArgs {};      // k_displace_grid's: a set of one tile
+
+// A_c of cascade c: the largest magnitude of its height keys.
+__device__ __forceinline__ float height_amplitude(const unsigned* minmax, int c)
+{
+    return fmaxf(fabsf(key_float(minmax[2 * c + 0])), fabsf(key_float(minmax[2 * c + 1])));
+}
+
+// ... of every cascade of a set, 0 beyond count.
+__device__ __forceinline__ void cascade_amplitudes(const unsigned* minmax, int count, float (&amp)[OCEAN_MAX_CASCADES])
+{
+#pragma unroll
+    for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) amp[c] = c < count ? height_amplitude(minmax, c) : 0.0f;
+}
+
+// The reference's normal from slopes and displacement derivatives (.vert:34-38), one sample's or the cascades' sums.
+__device__ __forceinline__ float3 vertex_normal(float sx, float sz, float ddx, float ddz, float choppy)
+{
+#pragma clang fp contract(off)
+    const float nx = -(sx / (1.0f + choppy * ddx));
+    const float nz = -(sz / (1.0f + choppy * ddz));
+    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
+    return make_float3(nx / len, 1.0f / len, nz / len);
+}
+
+// Vertex i of the grid: its rest point (WaterSurfaceMesh.cpp:514-518) and its uv.  False past the last vertex.
+__device__ __forceinline__ bool grid_vertex(const CascadeArgs& o, int i, float& px, float& pz, float& u, float& v)
+{
+#pragma clang fp contract(off)
+    const int side = o.grid + 1;
+    if (i >= side * side) return false;
+    const int half = o.grid / 2;
+    const int xi = i % side - half, yi = i / side - half;
+    px = (float)xi * o.vertex_distance; pz = (float)yi * o.vertex_distance;
+    u = (float)(xi + half) / (float)o.grid; v = (float)(yi + half) / (float)o.grid;
+    return true;
+}
 
 __device__ __forceinline__ float4 sample_linear_repeat(const float4* __restrict__ tex, int n, float u, float v)
 {
@@ -84,23 +131,17 @@ __device__ __forceinline__ float4 sample_lod(const float4* __restrict__ map, con
 __global__ void k_displace_grid(const GridArgs g)
 {
 #pragma clang fp contract(off)
-    const int side = g.grid + 1;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= side * side) return;
-    const int half = g.grid / 2;
-    const int xi = i % side - half, yi = i / side - half;          // WaterSurfaceMesh.cpp:514-518
-    const float px = (float)xi * g.vertex_distance, pz = (float)yi * g.vertex_distance;
-    const float u = (float)(xi + half) / (float)g.grid, v = (float)(yi + half) / (float)g.grid;
-    const float amp = fmaxf(fabsf(key_float(g.minmax[0])), fabsf(key_float(g.minmax[1])));
-    const float us = u * g.uv_scale, vs = v * g.uv_scale;          // .vert:26
-    float4 d = sample_linear_repeat(g.disp, g.n, us, vs);
+    float px, pz, u, v;
+    if (!grid_vertex(g, i, px, pz, u, v)) return;
+    const float amp = height_amplitude(g.s.minmax, 0);
+    const float us = u * g.s.uv_scale[0], vs = v * g.s.uv_scale[0];    // .vert:26
+    float4 d = sample_linear_repeat(g.s.disp, g.s.n, us, vs);
     d.y = d.y * amp;                                               // .vert:27
     g.positions[i] = make_float4(px + d.x, 0.0f + d.y, pz + d.z, d.w);   // .vert:28-29
-    const float4 sl = sample_linear_repeat(g.nrm, g.n, us, vs);    // .vert:33
-    const float nx = -(sl.x / (1.0f + g.choppy * sl.z));           // .vert:34-38
-    const float nz = -(sl.y / (1.0f + g.choppy * sl.w));
-    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
-    g.normals[i] = make_float4(nx / len, 1.0f / len, nz / len, 0.0f);
+    const float4 sl = sample_linear_repeat(g.s.nrm, g.s.n, us, vs);    // .vert:33
+    const float3 nv = vertex_normal(sl.x, sl.y, sl.z, sl.w, g.choppy);
+    g.normals[i] = make_float4(nv.x, nv.y, nv.z, 0.0f);
 }
 
 // Cascades (the reference's own to-do "Endless - solving the tiling artifacts", README.md:37-44): the
@@ -109,41 +150,65 @@ __global__ void k_displace_grid(const GridArgs g)
 // consumer only has to sum them: vertex = grid point + sum_c D_c(uv * s_c) (each height times its own amplitude A_c),
 // normal from the summed slopes and summed displacement derivatives with the reference's formula (.vert:34-38).
 // w carries the smallest Jacobian slot of the cascades (all 1 unless OCEAN_MODE_JACOBIAN).
-constexpr int OCEAN_MAX_CASCADES = 8;
-struct CascadeArgs {
-    GridArgs g;                        // disp / nrm / minmax of the FIRST tile of the cascade; n, grid, vertex_distance, choppy
-    int count;
-    size_t tile_texels;                // N * N
-    float uv_scale[OCEAN_MAX_CASCADES];
+struct SurfaceEval {
+    float dx, dy, dz, w;               // summed displacement (heights times their amplitude), smallest Jacobian slot
+    float sx, sz, ddx, ddz;            // summed normal-map samples
+    float jx, jz;                      // sum_c gain_c * (nrm_c.z, nrm_c.w): the Newton step's, 0 where JACOBIAN is not asked for
 };
+
+// The maps themselves as the sum's sampler; sample_lod at a per-cascade level is the other one (LodSampler, ocean_lod_kernels.h).
+struct MapSampler {
+    __device__ __forceinline__ void operator()(const CascadeSet& s, int c, float us, float vs, float4& d, float4& sl) const
+    {
+        d = sample_linear_repeat(s.disp + (size_t)c * s.tile_texels, s.n, us, vs);
+        sl = sample_linear_repeat(s.nrm + (size_t)c * s.tile_texels, s.n, us, vs);
+    }
+};
+
+// THE cascade sum at (u, v): every cascade's two samples, summed in cascade order from 0.0f / FLT_MAX, no contraction.  each(c, d, sl) is
+// shown the samples of cascade c before they are added (the spray emitters' per-cascade Jacobian).  UNROLLED = false: a runtime loop that
+// reads A_c from the keys (the vertex stages); true: unrolled, amplitudes in `amp` (cascade_amplitudes; the queries).  JACOBIAN adds the
+// Newton step's sums from `gain`.  amp / gain are read only where their flag is set.
+template <bool UNROLLED, bool JACOBIAN, class Sampler, class Each>
+__device__ __forceinline__ SurfaceEval cascade_sum(const CascadeSet& s, const float* amp, const float* gain, float u, float v,
+                                                   Sampler&& sample, Each&& each)
+{
+#pragma clang fp contract(off)
+    SurfaceEval e{0.0f, 0.0f, 0.0f, 3.402823466e+38f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma clang loop unroll_count(UNROLLED ? OCEAN_MAX_CASCADES : 1)
+    for (int c = 0; c < (UNROLLED ? OCEAN_MAX_CASCADES : s.count); ++c) {
+        if (UNROLLED && c >= s.count) break;
+        const float us = u * s.uv_scale[c], vs = v * s.uv_scale[c];
+        const float a = UNROLLED ? amp[c] : height_amplitude(s.minmax, c);
+        float4 d, sl;
+        sample(s, c, us, vs, d, sl);
+        each(c, d, sl);
+        e.dx = e.dx + d.x; e.dy = e.dy + d.y * a; e.dz = e.dz + d.z;
+        e.w = fminf(e.w, d.w);
+        e.sx = e.sx + sl.x; e.sz = e.sz + sl.y; e.ddx = e.ddx + sl.z; e.ddz = e.ddz + sl.w;
+        if constexpr (JACOBIAN) { e.jx = e.jx + sl.z * gain[c]; e.jz = e.jz + sl.w * gain[c]; }
+    }
+    return e;
+}
+
+struct NoEach { __device__ __forceinline__ void operator()(int, const float4&, const float4&) const {} };
+
+// The cascade vertex stage for vertex i, through either sampler.
+template <class Sampler>
+__device__ __forceinline__ void displace_grid_vertex(const CascadeArgs& a, int i, Sampler&& sample)
+{
+#pragma clang fp contract(off)
+    float px, pz, u, v;
+    if (!grid_vertex(a, i, px, pz, u, v)) return;
+    const SurfaceEval e = cascade_sum<false, false>(a.s, nullptr, nullptr, u, v, sample, NoEach{});
+    a.positions[i] = make_float4(px + e.dx, 0.0f + e.dy, pz + e.dz, e.w);
+    const float3 nv = vertex_normal(e.sx, e.sz, e.ddx, e.ddz, a.choppy);
+    a.normals[i] = make_float4(nv.x, nv.y, nv.z, 0.0f);
+}
 
 __global__ void k_displace_grid_cascades(const CascadeArgs a)
 {
-#pragma clang fp contract(off)
-    const GridArgs& g = a.g;
-    const int side = g.grid + 1;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= side * side) return;
-    const int half = g.grid / 2;
-    const int xi = i % side - half, yi = i / side - half;
-    const float px = (float)xi * g.vertex_distance, pz = (float)yi * g.vertex_distance;
-    const float u = (float)(xi + half) / (float)g.grid, v = (float)(yi + half) / (float)g.grid;
-    float dx = 0.0f, dy = 0.0f, dz = 0.0f, w = 3.402823466e+38f;
-    float sx = 0.0f, sz = 0.0f, ddx = 0.0f, ddz = 0.0f;
-    for (int c = 0; c < a.count; ++c) {
-        const float us = u * a.uv_scale[c], vs = v * a.uv_scale[c];
-        const float amp = fmaxf(fabsf(key_float(g.minmax[2 * c + 0])), fabsf(key_float(g.minmax[2 * c + 1])));
-        const float4 d = sample_linear_repeat(g.disp + (size_t)c * a.tile_texels, g.n, us, vs);
-        const float4 sl = sample_linear_repeat(g.nrm + (size_t)c * a.tile_texels, g.n, us, vs);
-        dx = dx + d.x; dy = dy + d.y * amp; dz = dz + d.z;
-        w = fminf(w, d.w);
-        sx = sx + sl.x; sz = sz + sl.y; ddx = ddx + sl.z; ddz = ddz + sl.w;
-    }
-    g.positions[i] = make_float4(px + dx, 0.0f + dy, pz + dz, w);
-    const float nx = -(sx / (1.0f + g.choppy * ddx));
-    const float nz = -(sz / (1.0f + g.choppy * ddz));
-    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
-    g.normals[i] = make_float4(nx / len, 1.0f / len, nz / len, 0.0f);
+    displace_grid_vertex(a, blockIdx.x * blockDim.x + threadIdx.x, MapSampler{});
 }
 
 // Mip chain of the maps (the reference's LOD hook: s_kUseMipMapping, WaterSurfaceMesh.h:216; Texture2D::GenerateMipmaps,
@@ -180,72 +245,44 @@ __global__ void k_mip_level(const MipArgs m)
 // One thread per point; K + 1 evaluations of 2 bilinear float4 gathers per cascade, all in fp32 in the order written below (no
 // contraction), which tests/surface_query.py repeats step for step.
 struct QueryArgs {
-    const float4* disp;                // maps of the FIRST tile of the cascade set (tile c at + c * tile_texels)
-    const float4* nrm;
-    const unsigned* minmax;            // height keys of the first tile (2 per tile)
+    CascadeSet s;
+    float gain[OCEAN_MAX_CASCADES];    // the Newton step's unit factor per cascade
     const float2* xz;                  // [points]
     float4* out_pos;                   // [points]  (P.x, P.y, P.z, min_c D_c.w)
     float4* out_nrm;                   // [points]  (n.x, n.y, n.z, residual)
-    size_t tile_texels;                // N * N
     unsigned points;
-    int n;                             // map size
-    int count;                         // cascades, 1 .. OCEAN_MAX_CASCADES
     int iterations;                    // K, 1 .. 32
     float grid;                        // grid_size
     float half;                        // grid_size / 2 (integer division, as the vertex stage's centring)
     float vertex_distance;
     float choppy;
-    float uv_scale[OCEAN_MAX_CASCADES];
-    float gain[OCEAN_MAX_CASCADES];
 };
 
-struct SurfaceEval {
-    float dx, dy, dz, w;               // summed displacement (heights times their amplitude), smallest Jacobian slot
-    float sx, sz, ddx, ddz;            // summed normal-map samples
-    float jx, jz;                      // sum_c gain_c * (nrm_c.z, nrm_c.w)
-};
-
-// The evaluation at a given (u, v): every cascade's two samples, summed as the cascade vertex stage sums them.  each(c, d, sl) is shown the
-// samples of cascade c before they are added -- for a caller that needs more of them than the sums (the spray emitters' per-cascade Jacobian).
-template <class Each>
-__device__ __forceinline__ SurfaceEval eval_surface_uv(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float u, float v, Each each)
+// The u (or v) of rest coordinate x on the grid a query describes (QueryArgs, or anything else with these three fields).
+template <class Args>
+__device__ __forceinline__ float rest_uv(const Args& a, float x)
 {
 #pragma clang fp contract(off)
-    SurfaceEval e{0.0f, 0.0f, 0.0f, 3.402823466e+38f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) {
-        if (c >= a.count) break;
-        const float us = u * a.uv_scale[c], vs = v * a.uv_scale[c];
-        const float4 d = sample_linear_repeat(a.disp + (size_t)c * a.tile_texels, a.n, us, vs);
-        const float4 sl = sample_linear_repeat(a.nrm + (size_t)c * a.tile_texels, a.n, us, vs);
-        each(c, d, sl);
-        e.dx = e.dx + d.x; e.dy = e.dy + d.y * amp[c]; e.dz = e.dz + d.z;
-        e.w = fminf(e.w, d.w);
-        e.sx = e.sx + sl.x; e.sz = e.sz + sl.y; e.ddx = e.ddx + sl.z; e.ddz = e.ddz + sl.w;
-        e.jx = e.jx + sl.z * a.gain[c]; e.jz = e.jz + sl.w * a.gain[c];
-    }
-    return e;
+    return (x / a.vertex_distance + a.half) / a.grid;
+}
+
+// The sum on the maps at a given (u, v), amplitudes in registers.  JACOBIAN as cascade_sum's: only the Newton step reads jx / jz.
+template <bool JACOBIAN, class Each>
+__device__ __forceinline__ SurfaceEval eval_surface_uv(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float u, float v, Each&& each)
+{
+    return cascade_sum<true, JACOBIAN>(a.s, amp, a.gain, u, v, MapSampler{}, each);
 }
 
 // ... at rest point (rx, rz): the (u, v) the query forms from it.
+template <bool JACOBIAN = false>
 __device__ __forceinline__ SurfaceEval eval_surface(const QueryArgs& a, const float (&amp)[OCEAN_MAX_CASCADES], float rx, float rz)
 {
-#pragma clang fp contract(off)
-    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
-    return eval_surface_uv(a, amp, u, v, [](int, const float4&, const float4&) {});
+    return eval_surface_uv<JACOBIAN>(a, amp, rest_uv(a, rx), rest_uv(a, rz), NoEach{});
 }
 
 __device__ __forceinline__ float clamp_jacobian(float j)
 {
     return fabsf(j) < 0.1f ? (j < 0.0f ? -0.1f : 0.1f) : j;
-}
-
-// Per-cascade amplitude (the height key's largest magnitude) of the cascade set, 0 beyond a.count.
-__device__ __forceinline__ void query_amplitudes(const QueryArgs& a, float (&amp)[OCEAN_MAX_CASCADES])
-{
-#pragma unroll
-    for (int c = 0; c < OCEAN_MAX_CASCADES; ++c)
-        amp[c] = c < a.count ? fmaxf(fabsf(key_float(a.minmax[2 * c + 0])), fabsf(key_float(a.minmax[2 * c + 1]))) : 0.0f;
 }
 
 // The K Newton steps from r_0 = q: the rest point whose displaced xz is q.
@@ -254,7 +291,7 @@ __device__ __forceinline__ void solve_rest(const QueryArgs& a, const float (&amp
 #pragma clang fp contract(off)
     rx = qx; rz = qz;
     for (int k = 0; k < a.iterations; ++k) {
-        const SurfaceEval e = eval_surface(a, amp, rx, rz);
+        const SurfaceEval e = eval_surface<true>(a, amp, rx, rz);
         const float ex = (rx + e.dx) - qx, ez = (rz + e.dz) - qz;
         const float jx = clamp_jacobian(1.0f + e.jx), jz = clamp_jacobian(1.0f + e.jz);
         rx = rx - ex / jx;
@@ -272,10 +309,8 @@ __device__ __forceinline__ void query_point(const QueryArgs& a, const float (&am
     const float px = rx + e.dx, pz = rz + e.dz;
     const float ex = px - qx, ez = pz - qz;
     pos = make_float4(px, 0.0f + e.dy, pz, e.w);
-    const float nx = -(e.sx / (1.0f + a.choppy * e.ddx));
-    const float nz = -(e.sz / (1.0f + a.choppy * e.ddz));
-    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
-    nrm = make_float4(nx / len, 1.0f / len, nz / len, sqrtf(ex * ex + ez * ez));
+    const float3 nv = vertex_normal(e.sx, e.sz, e.ddx, e.ddz, a.choppy);
+    nrm = make_float4(nv.x, nv.y, nv.z, sqrtf(ex * ex + ez * ez));
 }
 
 // H(x, z): only the height of the query at q (out_pos.y), without the normal.
@@ -292,7 +327,7 @@ __global__ void __launch_bounds__(256) k_query_surface(const QueryArgs a)
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.points) return;
     float amp[OCEAN_MAX_CASCADES];
-    query_amplitudes(a, amp);
+    cascade_amplitudes(a.s.minmax, a.s.count, amp);
     const float2 q = a.xz[i];
     float4 pos, nrm;
     query_point(a, amp, q.x, q.y, pos, nrm);
@@ -341,7 +376,7 @@ __global__ void __launch_bounds__(256) k_raycast_surface(const RaycastArgs r)
     const unsigned gshift = threadIdx.x & (64u - RAYCAST_LANES);       // the group's first bit in the wave's ballot
     const size_t ray = (size_t)blockIdx.x * (blockDim.x / RAYCAST_LANES) + threadIdx.x / RAYCAST_LANES;
     float amp[OCEAN_MAX_CASCADES];
-    query_amplitudes(a, amp);
+    cascade_amplitudes(a.s.minmax, a.s.count, amp);
     float hsum = 0.0f;
 #pragma unroll
     for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) hsum = hsum + amp[c];

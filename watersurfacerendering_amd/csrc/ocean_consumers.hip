@@ -38,6 +38,14 @@ static int last_frame(const ocean_ctx* c, uint32_t first_tile, LastFrame& f)
     return OCEAN_OK;
 }
 
+// Calls that read no frame: the consumers' stream only orders them among the other consumer calls.
+static void no_frame(const ocean_ctx* c, LastFrame& f)
+{
+    f = LastFrame{};
+    f.set = c->last_set;
+    f.st = stream_of(c, f.set);
+}
+
 // The consumer kernels write context-wide output buffers and run on the stream of the frame they read.  At pipeline depth > 1 consecutive
 // consumer calls land on different, mutually unordered chain streams: each call first makes its stream wait for the previous consumer launch,
 // so that two of them never write those buffers at once.
@@ -91,14 +99,12 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
     // the grid and mip buffers survive a new tile size (the grid's does not depend on it, ocean_build_mips re-allocates for mips_n != n),
     // their contents do not: they were made from maps that are gone
     c->mips_ready = false; c->grid_vertices = 0; c->grid_fresh = false; c->shaded_vertices = 0;
-    c->lod_ready = false;           // (the set of ocean_build_mips_tiles likewise: its capacity is in texels, whatever the tile size)
-    c->bnd_ready = false;           // (... and that of ocean_build_bounds_tiles)
+    c->lod.ready = c->bnd.ready = false;    // (the sets of ocean_build_mips_tiles / _bounds_tiles likewise: their capacity is in texels, whatever the tile size)
     std::fill(c->wave_count.begin(), c->wave_count.end(), 0u);      // (the wave sets name bins of a lattice that is gone; their buffers stay)
     if (!everything) return;
     free_and_null(c->grid_pos); free_and_null(c->grid_nrm); c->grid_capacity = 0;
     free_and_null(c->mips_disp); free_and_null(c->mips_nrm); c->mips_n = 0;
-    free_and_null(c->lod_disp); free_and_null(c->lod_nrm); c->lod_capacity = 0;
-    free_and_null(c->bnd_lo); free_and_null(c->bnd_hi); c->bnd_capacity = 0;
+    for (TileChains* t : {&c->lod, &c->bnd}) { free_and_null(t->a); free_and_null(t->b); t->capacity = 0; }
     free_and_null(c->hull); c->hull_points = 0;
     free_and_null(c->spray_scratch); c->spray_chunks = 0;
     free_and_null(c->waves); free_and_null(c->wave_anim); free_and_null(c->wave_scratch);
@@ -108,20 +114,47 @@ void ocean_consumers_release(ocean_ctx* c, bool everything)
 }
 
 // ---- vertex stage and mip chain ------------------------------------------------------------------------------------------------------------
-// Readiness, the output buffers for a grid of grid_size quads per side, and the launch arguments of the vertex stage from tile first_tile on.
-static int grid_args(ocean_ctx* c, uint32_t first_tile, uint32_t grid_size, float vertex_distance, float uv_scale, float choppy,
-                     LastFrame& f, GridArgs& g, uint32_t& verts)
+// What the kernels read of the cascade set of `count` tiles that frame f starts at (f = last_frame(c, first_tile)).
+static void cascade_set(const ocean_ctx* c, const LastFrame& f, uint32_t count, const float* uv_scales, CascadeSet& s)
+{
+    s.disp = f.disp; s.nrm = f.nrm; s.minmax = f.minmax;
+    s.tile_texels = f.n2; s.n = (int)c->n; s.count = (int)count;
+    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) s.uv_scale[i] = i < count ? uv_scales[i] : 0.0f;
+}
+
+// The vertex stage's three calls.  Readiness from tile first_tile on, the output buffers for a grid of grid_size quads per side, and the
+// kernels' arguments ...
+static int grid_args(ocean_ctx* c, uint32_t first_tile, uint32_t count, const float* uv_scales, uint32_t grid_size, float vertex_distance,
+                     float choppy, LastFrame& f, CascadeArgs& o, uint32_t& verts)
 {
     OCEAN_TRY(last_frame(c, first_tile, f));
     HIP_TRY(hipSetDevice(c->device));
     verts = (grid_size + 1) * (grid_size + 1);
     if (verts > c->grid_capacity)
         OCEAN_TRY(regrow(c, &c->grid_pos, &c->grid_nrm, (size_t)verts * sizeof(float4), c->grid_capacity, verts, [c] { c->grid_vertices = 0; }));
-    g.disp = f.disp; g.nrm = f.nrm; g.minmax = f.minmax;
-    g.positions = c->grid_pos; g.normals = c->grid_nrm;
-    g.n = (int)c->n; g.grid = (int)grid_size;
-    g.vertex_distance = vertex_distance; g.uv_scale = uv_scale; g.choppy = choppy;
+    o.positions = c->grid_pos; o.normals = c->grid_nrm;
+    o.grid = (int)grid_size; o.vertex_distance = vertex_distance; o.choppy = choppy;
+    cascade_set(c, f, count, uv_scales, o.s);
     return OCEAN_OK;
+}
+
+// ... the launch, one thread per vertex ...
+template <class Args>
+static int launch_grid(ocean_ctx* c, const LastFrame& f, void (*kernel)(Args), const Args& a, uint32_t verts)
+{
+    OCEAN_TRY(consumer_begin(c, f.st));
+    hipLaunchKernelGGL(kernel, dim3((verts + 255) / 256), dim3(256), 0, f.st, a);
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    c->grid_vertices = verts; c->grid_fresh = true;
+    return OCEAN_OK;
+}
+
+// ... and what the two cascade forms check of their arguments.
+static bool cascade_grid_valid(const ocean_ctx* c, uint32_t first_tile, uint32_t count, uint32_t grid_size, const float* uv_scales)
+{
+    return c && uv_scales && count != 0 && count <= (uint32_t)OCEAN_MAX_CASCADES && first_tile < c->tiles && first_tile + count <= c->tiles &&
+           grid_size != 0 && grid_size <= 8192;
 }
 
 extern "C" {
@@ -132,33 +165,19 @@ int ocean_displace_grid(ocean_t* c, uint32_t tile, uint32_t grid_size, float ver
     LastFrame f;
     GridArgs g;
     uint32_t verts;
-    OCEAN_TRY(grid_args(c, tile, grid_size, vertex_distance, uv_scale, choppy, f, g, verts));
-    OCEAN_TRY(consumer_begin(c, f.st));
-    hipLaunchKernelGGL(k_displace_grid, dim3((verts + 255) / 256), dim3(256), 0, f.st, g);
-    HIP_TRY(hipGetLastError());
-    OCEAN_TRY(consumer_end(c, f.st));
-    c->grid_vertices = verts; c->grid_fresh = true;
-    return OCEAN_OK;
+    OCEAN_TRY(grid_args(c, tile, 1, &uv_scale, grid_size, vertex_distance, choppy, f, g, verts));
+    return launch_grid(c, f, k_displace_grid, g, verts);
 }
 
 int ocean_displace_grid_cascades(ocean_t* c, uint32_t first_tile, uint32_t count, uint32_t grid_size, float vertex_distance,
                                  const float* uv_scales, float choppy)
 {
-    if (!c || !uv_scales || count == 0 || count > (uint32_t)OCEAN_MAX_CASCADES || first_tile >= c->tiles || first_tile + count > c->tiles ||
-        grid_size == 0 || grid_size > 8192)
-        return OCEAN_E_INVALID;
+    if (!cascade_grid_valid(c, first_tile, count, grid_size, uv_scales)) return OCEAN_E_INVALID;
     LastFrame f;
     CascadeArgs a;
     uint32_t verts;
-    OCEAN_TRY(grid_args(c, first_tile, grid_size, vertex_distance, 1.0f, choppy, f, a.g, verts));
-    a.count = (int)count; a.tile_texels = f.n2;
-    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) a.uv_scale[i] = i < count ? uv_scales[i] : 0.0f;
-    OCEAN_TRY(consumer_begin(c, f.st));
-    hipLaunchKernelGGL(k_displace_grid_cascades, dim3((verts + 255) / 256), dim3(256), 0, f.st, a);
-    HIP_TRY(hipGetLastError());
-    OCEAN_TRY(consumer_end(c, f.st));
-    c->grid_vertices = verts; c->grid_fresh = true;
-    return OCEAN_OK;
+    OCEAN_TRY(grid_args(c, first_tile, count, uv_scales, grid_size, vertex_distance, choppy, f, a, verts));
+    return launch_grid(c, f, k_displace_grid_cascades, a, verts);
 }
 
 int ocean_read_grid(ocean_t* c, float* positions, float* normals)
@@ -291,17 +310,13 @@ static int query_args(ocean_ctx* c, const ocean_surface* s, LastFrame& f, QueryA
         s->cascades > c->tiles - s->first_tile || s->grid_size == 0 || s->iterations > 32)
         return OCEAN_E_INVALID;
     OCEAN_TRY(last_frame(c, s->first_tile, f));
-    a.disp = f.disp; a.nrm = f.nrm; a.minmax = f.minmax;
-    a.tile_texels = f.n2;
-    a.n = (int)c->n;
-    a.count = (int)s->cascades;
+    cascade_set(c, f, s->cascades, s->uv_scales, a.s);
     a.iterations = s->iterations ? (int)s->iterations : 8;
     a.grid = (float)s->grid_size;
     a.half = (float)(s->grid_size / 2);
     a.vertex_distance = s->vertex_distance;
     a.choppy = s->choppy;
     for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) {
-        a.uv_scale[i] = i < s->cascades ? s->uv_scales[i] : 0.0f;
         a.gain[i] = 0.0f;
         if (i < s->cascades) {      // lambda_c * (s_c * L_c / (grid * vertex_distance)) of the frame that wrote tile c's maps
             const uint32_t tile = s->first_tile + i;
@@ -309,6 +324,14 @@ static int query_args(ocean_ctx* c, const ocean_surface* s, LastFrame& f, QueryA
         }
     }
     return OCEAN_OK;
+}
+
+// ... of the calls that only evaluate forward: the Newton iterations do not matter there.
+static int forward_args(ocean_ctx* c, const ocean_surface* s, LastFrame& f, QueryArgs& a)
+{
+    ocean_surface forward = *s;
+    forward.iterations = 0;
+    return query_args(c, &forward, f, a);
 }
 
 static int launch_query(QueryArgs& a, uint32_t points, const void* d_xz, void* d_out_pos, void* d_out_nrm, hipStream_t st)
@@ -351,7 +374,7 @@ static int foam_query_args(ocean_ctx* c, const ocean_surface* s, LastFrame& f, F
 {
     OCEAN_TRY(query_args(c, s, f, a.q));
     if (!c->foam_ready) return OCEAN_E_NOT_READY;
-    a.foam = c->foam[c->foam_cur] + s->first_tile * a.q.tile_texels;
+    a.foam = c->foam[c->foam_cur] + s->first_tile * a.q.s.tile_texels;
     a.q.out_pos = nullptr; a.q.out_nrm = nullptr;
     return OCEAN_OK;
 }
@@ -403,16 +426,80 @@ int ocean_raycast_surface_device(ocean_t* c, const ocean_surface* s, const ocean
 // ---- LOD sampling (include/ocean_consumers.h): mip chains of a tile range, the footprint-driven sampler's two consumers ----------------------
 static uint32_t log2_of(uint32_t n) { uint32_t l = 0; while ((1u << l) < n) ++l; return l; }
 
+// ---- the two sets of chains of a tile range (TileChains, ocean_ctx.h): the mip chains here, the min/max pyramids further down ---------------
+// The set covers the tiles [first, first + count) -- and, where a frame is given, was built from exactly that one (the most recent).
+static bool chains_cover(const ocean_ctx* c, const TileChains& t, uint32_t first, uint32_t count, const LastFrame* f)
+{
+    if (!t.ready || first < t.first || first + count > t.first + t.count) return false;
+    return !f || (t.frame == c->frame_serial && t.set == f->set);
+}
+
+static int chains_read_tile(ocean_ctx* c, const TileChains& t, uint32_t tile, float* a, float* b)
+{
+    if (tile >= c->tiles) return OCEAN_E_INVALID;
+    if (!c->prepared || !c->have_frame || !chains_cover(c, t, tile, 1, nullptr)) return OCEAN_E_NOT_READY;
+    HIP_TRY(hipSetDevice(c->device));
+    OCEAN_TRY(sync_all(c));
+    const size_t chain = ocean_mip_texels(c->n), at = (tile - t.first) * chain;
+    if (a) HIP_TRY(hipMemcpy(a, t.a + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
+    if (b) HIP_TRY(hipMemcpy(b, t.b + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
+    return OCEAN_OK;
+}
+
+static int chains_device(const ocean_ctx* c, const TileChains& t, void** d_a, void** d_b, uint32_t* first_tile, uint32_t* count, uint32_t* levels)
+{
+    if (d_a) *d_a = t.ready ? t.a : nullptr;
+    if (d_b) *d_b = t.ready ? t.b : nullptr;
+    if (first_tile) *first_tile = t.ready ? t.first : 0;
+    if (count) *count = t.ready ? t.count : 0;
+    if (levels) *levels = t.ready ? log2_of(c->n) : 0;
+    return OCEAN_OK;
+}
+
+// Both sets are built alike (ocean_lod_kernels.h, ocean_bounds_kernels.h): behind the most recent frame, one launch that takes blocks of
+// the maps src0 / src1 down to one texel each and, where N > MIP_BLOCK, a second for levels 7 .. log2 N from level 6 of the chains just
+// written (at texel sum_{k=1}^{5} (N >> k)^2 of a chain), one block per chain and tile.  launch(second, blocks) enqueues m on f.st.
+// From the first re-allocation to the end there is no set: a failure in between leaves none.
+template <class Args, class Sources, class Launch>
+static int build_chains(ocean_ctx* c, TileChains& t, uint32_t first_tile, uint32_t count, Args& m, Sources sources, Launch launch)
+{
+    if (!c || count == 0 || first_tile >= c->tiles || count > c->tiles - first_tile) return OCEAN_E_INVALID;
+    LastFrame f;
+    OCEAN_TRY(last_frame(c, first_tile, f));
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t n = c->n;
+    const size_t need = (size_t)count * ocean_mip_texels(n);
+    if (need > t.capacity) OCEAN_TRY(regrow(c, &t.a, &t.b, need * sizeof(float4), t.capacity, need, [&t] { t.ready = false; }));
+    t.ready = false;
+    sources(f, m);
+    m.dst[0] = t.a; m.dst[1] = t.b;
+    m.src_stride = f.n2; m.chain_texels = ocean_mip_texels(n); m.dst_offset = 0;
+    m.sw = (int)n; m.be = n < (uint32_t)MIP_BLOCK ? (int)n : MIP_BLOCK;
+    OCEAN_TRY(consumer_begin(c, f.st));
+    launch(false, (n / m.be) * (n / m.be), f.st);
+    if (n > (uint32_t)MIP_BLOCK) {
+        const size_t level6 = ((size_t)n * n - (size_t)(n >> 5) * (n >> 5)) / 3;
+        m.src[0] = t.a + level6; m.src[1] = t.b + level6;
+        m.src_stride = m.chain_texels;
+        m.sw = m.be = (int)(n / MIP_BLOCK);
+        m.dst_offset = level6 + (size_t)m.sw * m.sw;
+        launch(true, 1u, f.st);
+    }
+    HIP_TRY(hipGetLastError());
+    OCEAN_TRY(consumer_end(c, f.st));
+    t.first = first_tile; t.count = count; t.frame = c->frame_serial; t.set = f.set; t.ready = true;
+    return OCEAN_OK;
+}
+
 // The sampler's share of the launch arguments for the cascade set first_tile .. first_tile + cascades - 1 read from frame f: the set must
 // cover the range and have been built from exactly that frame -- whatever the footprints turn out to be.
 static int lod_set_args(const ocean_ctx* c, const ocean_lod* l, const LastFrame& f, uint32_t first_tile, uint32_t cascades, const float* uv_scales,
                         uint32_t grid_size, float vertex_distance, LodSet& s)
 {
-    if (!c->lod_ready || c->lod_frame != c->frame_serial || c->lod_set != f.set) return OCEAN_E_NOT_READY;
-    if (first_tile < c->lod_first || first_tile + cascades > c->lod_first + c->lod_count) return OCEAN_E_NOT_READY;
+    if (!chains_cover(c, c->lod, first_tile, cascades, &f)) return OCEAN_E_NOT_READY;
     s.chain_texels = ocean_mip_texels(c->n);
-    s.mips_disp = c->lod_disp + (first_tile - c->lod_first) * s.chain_texels;
-    s.mips_nrm = c->lod_nrm + (first_tile - c->lod_first) * s.chain_texels;
+    s.mips_disp = c->lod.a + (first_tile - c->lod.first) * s.chain_texels;
+    s.mips_nrm = c->lod.b + (first_tile - c->lod.first) * s.chain_texels;
     for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i)
         s.tpm[i] = i < cascades ? std::fabs((uv_scales[i] * (float)c->n) / ((float)grid_size * vertex_distance)) : 0.0f;
     s.scale = l->scale;
@@ -428,9 +515,7 @@ static bool lod_valid(const ocean_lod* l) { return l && l->scale > 0.0f && std::
 static int lod_point_args(ocean_ctx* c, const ocean_surface* s, const ocean_lod* l, LastFrame& f, LodPointArgs& a)
 {
     if (!c || !s || !lod_valid(l)) return OCEAN_E_INVALID;
-    ocean_surface forward = *s;
-    forward.iterations = 0;
-    OCEAN_TRY(query_args(c, &forward, f, a.q));
+    OCEAN_TRY(forward_args(c, s, f, a.q));
     return lod_set_args(c, l, f, s->first_tile, s->cascades, s->uv_scales, s->grid_size, s->vertex_distance, a.lod);
 }
 
@@ -450,60 +535,19 @@ extern "C" {
 
 int ocean_build_mips_tiles(ocean_t* c, uint32_t first_tile, uint32_t count)
 {
-    if (!c || count == 0 || first_tile >= c->tiles || count > c->tiles - first_tile) return OCEAN_E_INVALID;
-    LastFrame f;
-    OCEAN_TRY(last_frame(c, first_tile, f));
-    HIP_TRY(hipSetDevice(c->device));
-    const uint32_t n = c->n;
-    const size_t chain = ocean_mip_texels(n), need = (size_t)count * chain;
-    if (need > c->lod_capacity)
-        OCEAN_TRY(regrow(c, &c->lod_disp, &c->lod_nrm, need * sizeof(float4), c->lod_capacity, need, [c] { c->lod_ready = false; }));
-    c->lod_ready = false;           // until both launches are enqueued: a failure below leaves no set
     MipTilesArgs m;
-    m.src[0] = f.disp; m.src[1] = f.nrm;
-    m.dst[0] = c->lod_disp; m.dst[1] = c->lod_nrm;
-    m.src_stride = f.n2; m.chain_texels = chain; m.dst_offset = 0;
-    m.sw = (int)n; m.be = n < (uint32_t)MIP_BLOCK ? (int)n : MIP_BLOCK;
-    OCEAN_TRY(consumer_begin(c, f.st));
-    hipLaunchKernelGGL(k_mips_tiles, dim3((n / m.be) * (n / m.be), 2, count), dim3(256), 0, f.st, m);
-    if (n > (uint32_t)MIP_BLOCK) {  // levels 7 .. log2 N from level 6 of the chains: one block per map and tile
-        size_t level6 = 0;
-        for (uint32_t k = 1; k < 6; ++k) level6 += (size_t)(n >> k) * (n >> k);
-        m.src[0] = c->lod_disp + level6; m.src[1] = c->lod_nrm + level6;
-        m.src_stride = chain;
-        m.sw = m.be = (int)(n / MIP_BLOCK);
-        m.dst_offset = level6 + (size_t)m.sw * m.sw;
-        hipLaunchKernelGGL(k_mips_tiles, dim3(1, 2, count), dim3(256), 0, f.st, m);
-    }
-    HIP_TRY(hipGetLastError());
-    OCEAN_TRY(consumer_end(c, f.st));
-    c->lod_first = first_tile; c->lod_count = count;
-    c->lod_frame = c->frame_serial; c->lod_set = f.set;
-    c->lod_ready = true;
-    return OCEAN_OK;
+    return build_chains(c, c->lod, first_tile, count, m, [](const LastFrame& f, MipTilesArgs& a) { a.src[0] = f.disp; a.src[1] = f.nrm; },
+                        [&](bool, unsigned blocks, hipStream_t st) { hipLaunchKernelGGL(k_mips_tiles, dim3(blocks, 2, count), dim3(256), 0, st, m); });
 }
 
 int ocean_read_mips_tile(ocean_t* c, uint32_t tile, float* disp_mips, float* nrm_mips)
 {
-    if (!c || tile >= c->tiles) return OCEAN_E_INVALID;
-    if (!c->prepared || !c->have_frame || !c->lod_ready || tile < c->lod_first || tile - c->lod_first >= c->lod_count) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    OCEAN_TRY(sync_all(c));
-    const size_t chain = ocean_mip_texels(c->n), at = (tile - c->lod_first) * chain;
-    if (disp_mips) HIP_TRY(hipMemcpy(disp_mips, c->lod_disp + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
-    if (nrm_mips) HIP_TRY(hipMemcpy(nrm_mips, c->lod_nrm + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
-    return OCEAN_OK;
+    return c ? chains_read_tile(c, c->lod, tile, disp_mips, nrm_mips) : OCEAN_E_INVALID;
 }
 
 int ocean_device_mips_tiles(ocean_t* c, void** d_disp_mips, void** d_nrm_mips, uint32_t* first_tile, uint32_t* count, uint32_t* levels)
 {
-    if (!c) return OCEAN_E_INVALID;
-    if (d_disp_mips) *d_disp_mips = c->lod_ready ? c->lod_disp : nullptr;
-    if (d_nrm_mips) *d_nrm_mips = c->lod_ready ? c->lod_nrm : nullptr;
-    if (first_tile) *first_tile = c->lod_ready ? c->lod_first : 0;
-    if (count) *count = c->lod_ready ? c->lod_count : 0;
-    if (levels) *levels = c->lod_ready ? log2_of(c->n) : 0;
-    return OCEAN_OK;
+    return c ? chains_device(c, c->lod, d_disp_mips, d_nrm_mips, first_tile, count, levels) : OCEAN_E_INVALID;
 }
 
 void ocean_default_lod(ocean_lod* l)
@@ -532,9 +576,7 @@ int ocean_sample_surface_lod_device(ocean_t* c, const ocean_surface* s, const oc
 int ocean_displace_grid_lod(ocean_t* c, uint32_t first_tile, uint32_t count, uint32_t grid_size, float vertex_distance,
                             const float* uv_scales, float choppy, const ocean_lod* l)
 {
-    if (!c || !uv_scales || count == 0 || count > (uint32_t)OCEAN_MAX_CASCADES || first_tile >= c->tiles || first_tile + count > c->tiles ||
-        grid_size == 0 || grid_size > 8192 || !lod_valid(l))
-        return OCEAN_E_INVALID;
+    if (!cascade_grid_valid(c, first_tile, count, grid_size, uv_scales) || !lod_valid(l)) return OCEAN_E_INVALID;
     LastFrame f;
     LodGridArgs a{};
     uint32_t verts;
@@ -542,16 +584,9 @@ int ocean_displace_grid_lod(ocean_t* c, uint32_t first_tile, uint32_t count, uin
     // behind that: a re-allocation drains the context, and a frame it had to run again is a new frame
     OCEAN_TRY(last_frame(c, first_tile, f));
     OCEAN_TRY(lod_set_args(c, l, f, first_tile, count, uv_scales, grid_size, vertex_distance, a.lod));
-    OCEAN_TRY(grid_args(c, first_tile, grid_size, vertex_distance, 1.0f, choppy, f, a.a.g, verts));
+    OCEAN_TRY(grid_args(c, first_tile, count, uv_scales, grid_size, vertex_distance, choppy, f, a.a, verts));
     OCEAN_TRY(lod_set_args(c, l, f, first_tile, count, uv_scales, grid_size, vertex_distance, a.lod));
-    a.a.count = (int)count; a.a.tile_texels = f.n2;
-    for (uint32_t i = 0; i < (uint32_t)OCEAN_MAX_CASCADES; ++i) a.a.uv_scale[i] = i < count ? uv_scales[i] : 0.0f;
-    OCEAN_TRY(consumer_begin(c, f.st));
-    hipLaunchKernelGGL(k_displace_grid_lod, dim3((verts + 255) / 256), dim3(256), 0, f.st, a);
-    HIP_TRY(hipGetLastError());
-    OCEAN_TRY(consumer_end(c, f.st));
-    c->grid_vertices = verts; c->grid_fresh = true;
-    return OCEAN_OK;
+    return launch_grid(c, f, k_displace_grid_lod, a, verts);
 }
 
 }  // extern "C"
@@ -565,14 +600,11 @@ static int patch_args(ocean_ctx* c, const ocean_surface* s, const ocean_patch_qu
     for (uint32_t k = 0; k < q->planes; ++k)
         for (int j = 0; j < 4; ++j)
             if (!std::isfinite(q->plane[k][j])) return OCEAN_E_INVALID;
-    ocean_surface forward = *s;
-    forward.iterations = 0;
-    OCEAN_TRY(query_args(c, &forward, f, a.q));
-    if (!c->bnd_ready || c->bnd_frame != c->frame_serial || c->bnd_set != f.set) return OCEAN_E_NOT_READY;
-    if (s->first_tile < c->bnd_first || s->first_tile + s->cascades > c->bnd_first + c->bnd_count) return OCEAN_E_NOT_READY;
+    OCEAN_TRY(forward_args(c, s, f, a.q));
+    if (!chains_cover(c, c->bnd, s->first_tile, s->cascades, &f)) return OCEAN_E_NOT_READY;
     a.chain_texels = ocean_mip_texels(c->n);
-    a.lo = c->bnd_lo + (s->first_tile - c->bnd_first) * a.chain_texels;
-    a.hi = c->bnd_hi + (s->first_tile - c->bnd_first) * a.chain_texels;
+    a.lo = c->bnd.a + (s->first_tile - c->bnd.first) * a.chain_texels;
+    a.hi = c->bnd.b + (s->first_tile - c->bnd.first) * a.chain_texels;
     a.top = (int)log2_of(c->n);
     a.first_level = (int)c->bnd_first_level;
     a.pad = (int)q->pad_texels;
@@ -602,64 +634,30 @@ int ocean_build_bounds_tiles(ocean_t* c, uint32_t first_tile, uint32_t count, ui
     const uint32_t n = c->n, top = log2_of(n);
     if (first_level == 0) first_level = 1;
     if (first_level > top) return OCEAN_E_INVALID;
-    LastFrame f;
-    OCEAN_TRY(last_frame(c, first_tile, f));
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t chain = ocean_mip_texels(n), need = (size_t)count * chain;
-    if (need > c->bnd_capacity)
-        OCEAN_TRY(regrow(c, &c->bnd_lo, &c->bnd_hi, need * sizeof(float4), c->bnd_capacity, need, [c] { c->bnd_ready = false; }));
-    c->bnd_ready = false;           // until both launches are enqueued: a failure below leaves no set
     BoundsTilesArgs m;
-    m.src[0] = m.src[1] = f.disp;
-    m.dst[0] = c->bnd_lo; m.dst[1] = c->bnd_hi;
-    m.src_stride = f.n2; m.chain_texels = chain; m.dst_offset = 0;
-    m.sw = (int)n; m.be = n < (uint32_t)MIP_BLOCK ? (int)n : MIP_BLOCK;
-    m.level = 1;
+    const auto sources = [](const LastFrame& f, BoundsTilesArgs& a) { a.src[0] = a.src[1] = f.disp; };
     // (the second launch reads level 6 whatever first_level says: the first stores from min(first_level, 6) where there is a second)
-    m.store_from = (int)(n > (uint32_t)MIP_BLOCK && first_level > 6 ? 6 : first_level);
-    OCEAN_TRY(consumer_begin(c, f.st));
-    hipLaunchKernelGGL(k_bounds_tiles<false>, dim3((n / m.be) * (n / m.be), 1, count), dim3(256), 0, f.st, m);
-    if (n > (uint32_t)MIP_BLOCK) {  // levels 7 .. log2 N from level 6 of the two chains: one block per tile
-        size_t level6 = 0;
-        for (uint32_t k = 1; k < 6; ++k) level6 += (size_t)(n >> k) * (n >> k);
-        m.src[0] = c->bnd_lo + level6; m.src[1] = c->bnd_hi + level6;
-        m.src_stride = chain;
-        m.sw = m.be = (int)(n / MIP_BLOCK);
-        m.dst_offset = level6 + (size_t)m.sw * m.sw;
-        m.level = 7;
-        m.store_from = (int)first_level;
-        hipLaunchKernelGGL(k_bounds_tiles<true>, dim3(1, 1, count), dim3(256), 0, f.st, m);
-    }
-    HIP_TRY(hipGetLastError());
-    OCEAN_TRY(consumer_end(c, f.st));
-    c->bnd_first = first_tile; c->bnd_count = count; c->bnd_first_level = first_level;
-    c->bnd_frame = c->frame_serial; c->bnd_set = f.set;
-    c->bnd_ready = true;
+    const auto launch = [&](bool second, unsigned blocks, hipStream_t st) {
+        m.level = second ? 7 : 1;
+        m.store_from = (int)(!second && n > (uint32_t)MIP_BLOCK && first_level > 6 ? 6 : first_level);
+        if (second) hipLaunchKernelGGL(k_bounds_tiles<true>, dim3(blocks, 1, count), dim3(256), 0, st, m);
+        else hipLaunchKernelGGL(k_bounds_tiles<false>, dim3(blocks, 1, count), dim3(256), 0, st, m);
+    };
+    OCEAN_TRY(build_chains(c, c->bnd, first_tile, count, m, sources, launch));
+    c->bnd_first_level = first_level;
     return OCEAN_OK;
 }
 
 int ocean_read_bounds_tile(ocean_t* c, uint32_t tile, float* lo_chain, float* hi_chain)
 {
-    if (!c || tile >= c->tiles) return OCEAN_E_INVALID;
-    if (!c->prepared || !c->have_frame || !c->bnd_ready || tile < c->bnd_first || tile - c->bnd_first >= c->bnd_count) return OCEAN_E_NOT_READY;
-    HIP_TRY(hipSetDevice(c->device));
-    OCEAN_TRY(sync_all(c));
-    const size_t chain = ocean_mip_texels(c->n), at = (tile - c->bnd_first) * chain;
-    if (lo_chain) HIP_TRY(hipMemcpy(lo_chain, c->bnd_lo + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
-    if (hi_chain) HIP_TRY(hipMemcpy(hi_chain, c->bnd_hi + at, chain * sizeof(float4), hipMemcpyDeviceToHost));
-    return OCEAN_OK;
+    return c ? chains_read_tile(c, c->bnd, tile, lo_chain, hi_chain) : OCEAN_E_INVALID;
 }
 
 int ocean_device_bounds_tiles(ocean_t* c, void** d_lo, void** d_hi, uint32_t* first_tile, uint32_t* count, uint32_t* levels, uint32_t* first_level)
 {
     if (!c) return OCEAN_E_INVALID;
-    if (d_lo) *d_lo = c->bnd_ready ? c->bnd_lo : nullptr;
-    if (d_hi) *d_hi = c->bnd_ready ? c->bnd_hi : nullptr;
-    if (first_tile) *first_tile = c->bnd_ready ? c->bnd_first : 0;
-    if (count) *count = c->bnd_ready ? c->bnd_count : 0;
-    if (levels) *levels = c->bnd_ready ? log2_of(c->n) : 0;
-    if (first_level) *first_level = c->bnd_ready ? c->bnd_first_level : 0;
-    return OCEAN_OK;
+    if (first_level) *first_level = c->bnd.ready ? c->bnd_first_level : 0;
+    return chains_device(c, c->bnd, d_lo, d_hi, first_tile, count, levels);
 }
 
 void ocean_default_patch_query(ocean_patch_query* q)
@@ -750,9 +748,7 @@ static int spray_args(ocean_ctx* c, const ocean_surface* s, const ocean_spray* p
     if (!c || !s || !p || p->nx == 0 || p->ny == 0 || (uint64_t)p->nx * p->ny > ((uint64_t)1 << 24) || p->thin_log2 > 16 ||
         !std::isfinite(p->threshold) || !std::isfinite(p->gain) || !std::isfinite(p->min_rise) || p->gain < 0.0f)
         return OCEAN_E_INVALID;
-    ocean_surface forward = *s;
-    forward.iterations = 0;
-    OCEAN_TRY(query_args(c, &forward, f, a.q));
+    OCEAN_TRY(forward_args(c, s, f, a.q));
     const int mode = c->set_mode[f.set];            // of the frame that wrote these maps, not of the next one
     if (mode != OCEAN_MODE_FULL7 && mode != OCEAN_MODE_JACOBIAN) return OCEAN_E_UNSUPPORTED;
     a.from_slot = mode == OCEAN_MODE_JACOBIAN;
@@ -1140,9 +1136,7 @@ static int wave_eval_args(ocean_ctx* c, const ocean_surface* s, float t, bool in
     if (!c->prepared) return OCEAN_E_NOT_READY;
     for (uint32_t i = 0; i < s->cascades; ++i)
         if (!wave_set_exists(c, s->first_tile + i)) return OCEAN_E_NOT_READY;
-    f = LastFrame{};
-    f.set = c->last_set;
-    f.st = stream_of(c, f.set);            // no frame is read: the consumers' stream only orders the call among the other consumer calls
+    no_frame(c, f);
     a.set.rows = c->waves + (size_t)s->first_tile * WAVES_MAX;
     a.set.anim = c->wave_anim;
     a.cascades = (int)s->cascades;
@@ -1370,14 +1364,6 @@ static int sky_dev(const ocean_sky* s, SkyDev& d)
     }
     d.sun_intensity = s->sun_intensity;
     return OCEAN_OK;
-}
-
-// Calls that read no frame: the consumers' stream only orders them among the other consumer calls.
-static void no_frame(const ocean_ctx* c, LastFrame& f)
-{
-    f = LastFrame{};
-    f.set = c->last_set;
-    f.st = stream_of(c, f.set);
 }
 
 static unsigned point_blocks(uint32_t count)

@@ -82,6 +82,18 @@ inline void ocean_launch_bytes_per_texel(bool half_inter, bool jacobian, bool h0
     out[2] = pair0 + 2 + 16 + (jacobian ? 4 : 0);
 }
 
+// Chains of a tile range built from one frame: [count][ocean_mip_texels(N)] float4 per buffer, each tile's levels 1 .. log2 N tightly packed.
+// The set remembers the frame it was built from, so that a consumer of another frame finds it stale.
+struct TileChains {
+    float4* a = nullptr;
+    float4* b = nullptr;
+    size_t capacity = 0;            // texels per buffer
+    uint32_t first = 0, count = 0;  // the built range [first, first + count)
+    uint64_t frame = 0;             // frame_serial and chain of the frame the set was built from
+    int set = 0;
+    bool ready = false;             // a set has been built since the last ocean_prepare / new tile size
+};
+
 struct ocean_ctx {
     OceanTuning tune;               // the heuristics' constants (defaults above; nothing changes them at run time)
     int occ_n = 0;                  // tile size occ_* were asked for: resident workgroups per compute unit of the single-transform z pass and of
@@ -184,25 +196,12 @@ struct ocean_ctx {
     float4* mips_nrm = nullptr;
     uint32_t mips_n = 0;            // tile size the two buffers were allocated for
     bool mips_ready = false;
-    // Mip chains of a tile range (ocean_build_mips_tiles): [lod_count][ocean_mip_texels(N)] per map, each tile in the packed layout above.
-    // What the LOD sampler reads, so the set remembers the frame it was built from: a consumer of another frame finds it stale.
-    float4* lod_disp = nullptr;
-    float4* lod_nrm = nullptr;
-    size_t lod_capacity = 0;        // texels per buffer
-    uint32_t lod_first = 0, lod_count = 0;  // the built range [lod_first, lod_first + lod_count)
-    uint64_t lod_frame = 0;         // frame_serial and chain of the frame the set was built from
-    int lod_set = 0;
-    bool lod_ready = false;         // a set has been built since the last ocean_prepare / new tile size
-    // Min/max pyramids of the displacement maps of a tile range (ocean_build_bounds_tiles): [bnd_count][ocean_mip_texels(N)] per chain, the
-    // same packed layout; levels below bnd_first_level are not stored.  What ocean_patch_bounds reads: it remembers its frame as the set above.
-    float4* bnd_lo = nullptr;
-    float4* bnd_hi = nullptr;
-    size_t bnd_capacity = 0;        // texels per buffer
-    uint32_t bnd_first = 0, bnd_count = 0;  // the built range [bnd_first, bnd_first + bnd_count)
-    uint32_t bnd_first_level = 1;   // 1 .. log2 N
-    uint64_t bnd_frame = 0;         // frame_serial and chain of the frame the set was built from
-    int bnd_set = 0;
-    bool bnd_ready = false;         // a set has been built since the last ocean_prepare / new tile size
+    // Mip chains of a tile range (ocean_build_mips_tiles): a = displacement, b = normal.  What the LOD sampler reads.
+    TileChains lod;
+    // Min/max pyramids of the displacement maps of a tile range (ocean_build_bounds_tiles): a = lo, b = hi; levels below bnd_first_level
+    // (1 .. log2 N) are not stored.  What ocean_patch_bounds reads.
+    TileChains bnd;
+    uint32_t bnd_first_level = 1;
     uint64_t frame_serial = 0;      // successful frame enqueues of the context's whole life (never reset: no two frames share a number)
     std::vector<float> prep_length;        // [tiles] tile length the most recent ocean_prepare built the spectrum for
     std::vector<float> set_lambda[MAXD];    // [tiles] lambda and tile length of the frame that wrote each chain's maps

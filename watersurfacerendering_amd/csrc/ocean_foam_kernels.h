@@ -166,7 +166,7 @@ inline unsigned foam_blocks(unsigned n, unsigned)
 // out = (foam, r.x, r.z, |P(r).xz - q|).  One thread per point; fp32, no contraction (tests/foam.py repeats it).
 struct FoamQueryArgs {
     QueryArgs q;             // the surface (q.out_pos / q.out_nrm unused)
-    const float* foam;       // F of the FIRST tile of the cascade set (tile c at + c * q.tile_texels)
+    const float* foam;       // F of the FIRST tile of the cascade set (tile c at + c * q.s.tile_texels)
     float4* out;             // [points]
 };
 
@@ -191,18 +191,18 @@ __global__ void __launch_bounds__(256) k_query_foam(const FoamQueryArgs fa)
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.points) return;
     float amp[OCEAN_MAX_CASCADES];
-    query_amplitudes(a, amp);
+    cascade_amplitudes(a.s.minmax, a.s.count, amp);
     const float2 q = a.xz[i];
     float rx, rz;
     solve_rest(a, amp, q.x, q.y, rx, rz);
     const SurfaceEval e = eval_surface(a, amp, rx, rz);
     const float ex = (rx + e.dx) - q.x, ez = (rz + e.dz) - q.y;
-    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
+    const float u = rest_uv(a, rx), v = rest_uv(a, rz);
     float foam = 0.0f;
 #pragma unroll
     for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) {
-        if (c >= a.count) break;
-        foam = fmaxf(foam, sample_linear_repeat_scalar(fa.foam + (size_t)c * a.tile_texels, a.n, u * a.uv_scale[c], v * a.uv_scale[c]));
+        if (c >= a.s.count) break;
+        foam = fmaxf(foam, sample_linear_repeat_scalar(fa.foam + (size_t)c * a.s.tile_texels, a.s.n, u * a.s.uv_scale[c], v * a.s.uv_scale[c]));
     }
     fa.out[i] = make_float4(foam, rx, rz, sqrtf(ex * ex + ez * ez));
 }

@@ -1,6 +1,6 @@
 // ocean_lod_kernels.h -- LOD sampling (include/ocean_consumers.h: ocean_build_mips_tiles, ocean_sample_surface_lod, ocean_displace_grid_lod),
-// compiled into ocean_consumers.hip only: the mip chains of a whole tile range in at most two launches, and the two kernels that read the
-// maps through the footprint-driven sampler (sample_lod, beside sample_linear_repeat in ocean_consumer_kernels.h).
+// compiled into ocean_consumers.hip only: the mip chains of a whole tile range in at most two launches, and the two kernels that run
+// the cascade sum (cascade_sum, ocean_consumer_kernels.h) through the footprint-driven sampler (sample_lod, beside sample_linear_repeat there).
 #pragma once
 #include "ocean_consumer_kernels.h"
 
@@ -94,8 +94,24 @@ struct LodSet {
     int lmax;                          // log2 N, or min(log2 N, ocean_lod.max_level)
 };
 
+// sample_lod as the cascade sum's sampler: cascade c at the level that fits fs * tpm[c] texels, both maps at the same one.  lambda is the
+// coarsest level + blend any cascade has used so far (the point form reports it; the grid form leaves it alone).
+struct LodSampler {
+    const LodSet& lod;
+    float fs;                          // footprint in mesh metres, times lod.scale
+    float lambda = 0.0f;
+    __device__ __forceinline__ void operator()(const CascadeSet& s, int c, float us, float vs, float4& d, float4& sl)
+    {
+        int lev; float t;
+        lod_level(fs * lod.tpm[c], lod.lmax, lod.top, lev, t);
+        d = sample_lod(s.disp + (size_t)c * s.tile_texels, lod.mips_disp + (size_t)c * lod.chain_texels, s.n, lev, t, us, vs);
+        sl = sample_lod(s.nrm + (size_t)c * s.tile_texels, lod.mips_nrm + (size_t)c * lod.chain_texels, s.n, lev, t, us, vs);
+        lambda = fmaxf(lambda, (float)lev + t);
+    }
+};
+
 // Forward evaluation at rest point (x, z) with footprint f: out_pos / out_nrm of ocean_sample_surface_lod.  fp32, no contraction, in the
-// order include/ocean_consumers.h states and tests/lod.py repeats.
+// order include/ocean_consumers.h states and tests/lod.py repeats: the cascade sum (ocean_consumer_kernels.h) through the sampler above.
 struct LodPointArgs {
     QueryArgs q;                       // the surface (q.xz / iterations / gain unused)
     LodSet lod;
@@ -110,27 +126,11 @@ __global__ void __launch_bounds__(256) k_sample_surface_lod(const LodPointArgs p
     if (i >= a.points) return;
     const float* in = p.xzf + (size_t)i * 3;
     const float x = in[0], z = in[1], f = in[2];
-    const float u = (x / a.vertex_distance + a.half) / a.grid, v = (z / a.vertex_distance + a.half) / a.grid;
-    const float fs = f * p.lod.scale;
-    float dx = 0.0f, dy = 0.0f, dz = 0.0f, w = 3.402823466e+38f;
-    float sx = 0.0f, sz = 0.0f, ddx = 0.0f, ddz = 0.0f, lambda = 0.0f;
-    for (int c = 0; c < a.count; ++c) {
-        const float us = u * a.uv_scale[c], vs = v * a.uv_scale[c];
-        const float amp = fmaxf(fabsf(key_float(a.minmax[2 * c + 0])), fabsf(key_float(a.minmax[2 * c + 1])));
-        int lev; float t;
-        lod_level(fs * p.lod.tpm[c], p.lod.lmax, p.lod.top, lev, t);
-        const float4 d = sample_lod(a.disp + (size_t)c * a.tile_texels, p.lod.mips_disp + (size_t)c * p.lod.chain_texels, a.n, lev, t, us, vs);
-        const float4 sl = sample_lod(a.nrm + (size_t)c * a.tile_texels, p.lod.mips_nrm + (size_t)c * p.lod.chain_texels, a.n, lev, t, us, vs);
-        dx = dx + d.x; dy = dy + d.y * amp; dz = dz + d.z;
-        w = fminf(w, d.w);
-        sx = sx + sl.x; sz = sz + sl.y; ddx = ddx + sl.z; ddz = ddz + sl.w;
-        lambda = fmaxf(lambda, (float)lev + t);
-    }
-    a.out_pos[i] = make_float4(x + dx, 0.0f + dy, z + dz, w);
-    const float nx = -(sx / (1.0f + a.choppy * ddx));
-    const float nz = -(sz / (1.0f + a.choppy * ddz));
-    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
-    a.out_nrm[i] = make_float4(nx / len, 1.0f / len, nz / len, lambda);
+    LodSampler sample{p.lod, f * p.lod.scale};
+    const SurfaceEval e = cascade_sum<false, false>(a.s, nullptr, nullptr, rest_uv(a, x), rest_uv(a, z), sample, NoEach{});
+    a.out_pos[i] = make_float4(x + e.dx, 0.0f + e.dy, z + e.dz, e.w);
+    const float3 nv = vertex_normal(e.sx, e.sz, e.ddx, e.ddz, a.choppy);
+    a.out_nrm[i] = make_float4(nv.x, nv.y, nv.z, sample.lambda);
 }
 
 // k_displace_grid_cascades with every sample through the sampler at footprint |vertex_distance|: the level is the same for every vertex of a
@@ -143,34 +143,7 @@ struct LodGridArgs {
 __global__ void __launch_bounds__(256) k_displace_grid_lod(const LodGridArgs p)
 {
 #pragma clang fp contract(off)
-    const CascadeArgs& a = p.a;
-    const GridArgs& g = a.g;
-    const int side = g.grid + 1;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= side * side) return;
-    const int half = g.grid / 2;
-    const int xi = i % side - half, yi = i / side - half;
-    const float px = (float)xi * g.vertex_distance, pz = (float)yi * g.vertex_distance;
-    const float u = (float)(xi + half) / (float)g.grid, v = (float)(yi + half) / (float)g.grid;
-    const float fs = fabsf(g.vertex_distance) * p.lod.scale;
-    float dx = 0.0f, dy = 0.0f, dz = 0.0f, w = 3.402823466e+38f;
-    float sx = 0.0f, sz = 0.0f, ddx = 0.0f, ddz = 0.0f;
-    for (int c = 0; c < a.count; ++c) {
-        const float us = u * a.uv_scale[c], vs = v * a.uv_scale[c];
-        const float amp = fmaxf(fabsf(key_float(g.minmax[2 * c + 0])), fabsf(key_float(g.minmax[2 * c + 1])));
-        int lev; float t;
-        lod_level(fs * p.lod.tpm[c], p.lod.lmax, p.lod.top, lev, t);
-        const float4 d = sample_lod(g.disp + (size_t)c * a.tile_texels, p.lod.mips_disp + (size_t)c * p.lod.chain_texels, g.n, lev, t, us, vs);
-        const float4 sl = sample_lod(g.nrm + (size_t)c * a.tile_texels, p.lod.mips_nrm + (size_t)c * p.lod.chain_texels, g.n, lev, t, us, vs);
-        dx = dx + d.x; dy = dy + d.y * amp; dz = dz + d.z;
-        w = fminf(w, d.w);
-        sx = sx + sl.x; sz = sz + sl.y; ddx = ddx + sl.z; ddz = ddz + sl.w;
-    }
-    g.positions[i] = make_float4(px + dx, 0.0f + dy, pz + dz, w);
-    const float nx = -(sx / (1.0f + g.choppy * ddx));
-    const float nz = -(sz / (1.0f + g.choppy * ddz));
-    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
-    g.normals[i] = make_float4(nx / len, 1.0f / len, nz / len, 0.0f);
+    displace_grid_vertex(p.a, blockIdx.x * blockDim.x + threadIdx.x, LodSampler{p.lod, fabsf(p.a.vertex_distance) * p.lod.scale});
 }
 
 }  // namespace ocean

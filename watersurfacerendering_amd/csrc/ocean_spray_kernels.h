@@ -65,7 +65,7 @@ __device__ __forceinline__ bool spray_vertex(const SprayArgs& s, const float (&a
     const float px = (float)xi * a.vertex_distance, pz = (float)yi * a.vertex_distance;
     const float u = (float)(int)((unsigned)xi + (unsigned)s.half) / a.grid, v = (float)(int)((unsigned)yi + (unsigned)s.half) / a.grid;
     float j = 3.402823466e+38f;
-    const SurfaceEval e = eval_surface_uv(a, amp, u, v, [&](int c, const float4& d, const float4& sl) {
+    const SurfaceEval e = eval_surface_uv<false>(a, amp, u, v, [&](int c, const float4& d, const float4& sl) {
 #pragma clang fp contract(off)
         const float jc = s.from_slot ? d.w : (1.0f + s.lam[c] * sl.z) * (1.0f + s.lam[c] * sl.w);
         j = fminf(j, jc);
@@ -84,9 +84,9 @@ __device__ __forceinline__ bool spray_vertex(const SprayArgs& s, const float (&a
 
 __device__ __forceinline__ void spray_amplitudes(const SprayArgs& s, float (&amp)[OCEAN_MAX_CASCADES], float (&tamp)[OCEAN_MAX_CASCADES])
 {
-    query_amplitudes(s.q, amp);
+    cascade_amplitudes(s.q.s.minmax, s.q.s.count, amp);
     if (s.twinned) {
-        twin_amplitudes(s.q, s.tw, tamp);
+        cascade_amplitudes(s.tw.minmax, s.q.s.count, tamp);
     } else {
 #pragma unroll
         for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) tamp[c] = 0.0f;

@@ -14,15 +14,7 @@ struct TwinMaps {
     const unsigned* minmax;            // height keys of the first twin: A' = the largest magnitude of dh/dt
 };
 
-// Per-cascade A' (as query_amplitudes, from the twins' keys), 0 beyond a.count.
-__device__ __forceinline__ void twin_amplitudes(const QueryArgs& a, const TwinMaps& tw, float (&tamp)[OCEAN_MAX_CASCADES])
-{
-#pragma unroll
-    for (int c = 0; c < OCEAN_MAX_CASCADES; ++c)
-        tamp[c] = c < a.count ? fmaxf(fabsf(key_float(tw.minmax[2 * c + 0])), fabsf(key_float(tw.minmax[2 * c + 1]))) : 0.0f;
-}
-
-// V at a given (u, v): the twins' displacement maps at the uv the sources are sampled at, summed in cascade order from 0.0f.
+// V at a given (u, v), tamp = the twins' A' (cascade_amplitudes of tw.minmax): the twins' displacement maps at the uv the sources are sampled at, summed in cascade order from 0.0f.
 // One bilinear float4 gather per cascade.
 __device__ __forceinline__ void water_velocity_uv(const QueryArgs& a, const TwinMaps& tw, const float (&tamp)[OCEAN_MAX_CASCADES], float u, float v,
                                                   float& vx, float& vy, float& vz)
@@ -31,8 +23,8 @@ __device__ __forceinline__ void water_velocity_uv(const QueryArgs& a, const Twin
     vx = 0.0f; vy = 0.0f; vz = 0.0f;
 #pragma unroll
     for (int c = 0; c < OCEAN_MAX_CASCADES; ++c) {
-        if (c >= a.count) break;
-        const float4 d = sample_linear_repeat(tw.disp + (size_t)c * a.tile_texels, a.n, u * a.uv_scale[c], v * a.uv_scale[c]);
+        if (c >= a.s.count) break;
+        const float4 d = sample_linear_repeat(tw.disp + (size_t)c * a.s.tile_texels, a.s.n, u * a.s.uv_scale[c], v * a.s.uv_scale[c]);
         vx = vx + d.x; vy = vy + d.y * tamp[c]; vz = vz + d.z;
     }
 }
@@ -41,9 +33,7 @@ __device__ __forceinline__ void water_velocity_uv(const QueryArgs& a, const Twin
 __device__ __forceinline__ void water_velocity(const QueryArgs& a, const TwinMaps& tw, const float (&tamp)[OCEAN_MAX_CASCADES], float rx, float rz,
                                                float& vx, float& vy, float& vz)
 {
-#pragma clang fp contract(off)
-    const float u = (rx / a.vertex_distance + a.half) / a.grid, v = (rz / a.vertex_distance + a.half) / a.grid;
-    water_velocity_uv(a, tw, tamp, u, v, vx, vy, vz);
+    water_velocity_uv(a, tw, tamp, rest_uv(a, rx), rest_uv(a, rz), vx, vy, vz);
 }
 
 // Velocity query: one thread per point; the K + 1 evaluations of the surface query, then one more gather per cascade from the twins.
@@ -61,8 +51,8 @@ __global__ void __launch_bounds__(256) k_query_velocity(const VelocityArgs va)
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.points) return;
     float amp[OCEAN_MAX_CASCADES], tamp[OCEAN_MAX_CASCADES];
-    query_amplitudes(a, amp);
-    twin_amplitudes(a, va.tw, tamp);
+    cascade_amplitudes(a.s.minmax, a.s.count, amp);
+    cascade_amplitudes(va.tw.minmax, a.s.count, tamp);
     const float2 q = a.xz[i];
     float rx, rz;
     solve_rest(a, amp, q.x, q.y, rx, rz);

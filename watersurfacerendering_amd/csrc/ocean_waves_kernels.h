@@ -166,12 +166,7 @@ struct WaveEval {
 // The wave sets of every cascade at rest point (rx, rz).
 __device__ __forceinline__ WaveEval eval_waves(const WaveEvalArgs& a, const float4* __restrict__ anim, float rx, float rz)
 {
-    float u, v;
-    {
-#pragma clang fp contract(off)
-        u = (rx / a.vertex_distance + a.half) / a.grid;
-        v = (rz / a.vertex_distance + a.half) / a.grid;
-    }
+    const float u = rest_uv(a, rx), v = rest_uv(a, rz);
     WaveEval e{0.0f, 0.0f, 0.0f, 3.402823466e+38f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (int c = 0; c < a.cascades; ++c) {
         float fx, fz;
@@ -221,11 +216,8 @@ __device__ __forceinline__ WaveEval eval_waves(const WaveEvalArgs& a, const floa
 
 __device__ __forceinline__ float4 waves_normal(const WaveEvalArgs& a, const WaveEval& e, float w)
 {
-#pragma clang fp contract(off)
-    const float nx = -(e.sx / (1.0f + a.choppy * e.ddx));
-    const float nz = -(e.sz / (1.0f + a.choppy * e.ddz));
-    const float len = sqrtf(nx * nx + 1.0f + nz * nz);
-    return make_float4(nx / len, 1.0f / len, nz / len, w);
+    const float3 n = vertex_normal(e.sx, e.sz, e.ddx, e.ddz, a.choppy);
+    return make_float4(n.x, n.y, n.z, w);
 }
 
 // Forward evaluation: what the cascade vertex stage would draw for a vertex at rest point xz[i], from the wave sets alone.
